@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- walker-steps/s of the fused HIP annealed-SDE sampler (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lj13|dw4|aldp22|lj55]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lj13|dw4|aldp22|lj55] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload (BASELINE.json configs[2], the configuration the metric is quoted on): LJ13 (13 particles x 3D), EGNN
@@ -11,8 +11,13 @@ diffusion_scale 1, NOT-debiased reverse VE-SDE, resampling off, 65 536 walkers P
 from the mean-free prior.  One "step" = one Euler-Maruyama step of all walkers: EDM-preconditioned EGNN forward + drift +
 noise + update + remove_mean, all inside the fused kernel `egnn_kernel<...,SAMPLER>`; the K timed steps run as K/c
 launches of c = gcd(K, W) steps each (the warm-up uses the same launch size, so every launch of the kernel in this
-process is equal and the rocprof average is comparable).  After the timed region separately timed loops give the
-roofline of the target's log-density+force kernel and the debiased (Feynman-Kac) regime.
+process is equal and the rocprof average is comparable).  A plain run does only that: set-up, a clock warm-up on a copy
+of the walkers, the W warm-up steps, the K timed steps, the result line.  `--full` adds the secondary legs: the roofline
+of the target's log-density+force kernel and the debiased (Feynman-Kac) regime in front of the timed region, the
+whole-integrate_sde and small-batch legs and the CPU baselines behind it.
+
+`--dump-outputs DIR` writes the walkers the timed steps computed, as DIR/walkers.npy (float32; inputs are seeded, so two
+builds run with the same arguments can be compared output for output).
 
 `--config` selects the other GPU configurations of BASELINE.json at their per-GPU shard (dw4: 65 536 walkers; aldp22:
 4 096 = 16 384 / 4 GPUs; lj55: 32 768 = 262 144 / 8 GPUs): same measurement, same JSON fields.
@@ -41,6 +46,7 @@ ACHIEVABLE_HBM_GBS = 6300.0      # MI355X_MICROARCH.md: measured float4 copy (79
 MFMA16_FLOP = 2 * 32 * 32 * 16   # one v_mfma_f32_32x32x16_{bf16,f16}
 MFMA32_FLOP = 2 * 32 * 32 * 2    # one v_mfma_f32_32x32x2_f32
 NOMINAL_CLOCK_HZ = 2.4e9
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most 64 MB on disk
 
 # name -> particles, dims, walkers per GPU, sigma_min, target kind
 CONFIGS = {
@@ -77,6 +83,18 @@ def pmc_summary():
             return json.load(f)
     except Exception:
         return None
+
+
+def dump_walkers(path, x):
+    """path/walkers.npy: the walkers [rows, n*d] the timed steps left, float32.  A batch above DUMP_MAX_BYTES is written
+    as a fixed sample of its rows (seed 0, in walker order): the same rows in every run with the same arguments."""
+    import numpy as np
+
+    a = x.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_BYTES // a[0].nbytes, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "walkers.npy"), a)
 
 
 def self_launch(args):
@@ -679,7 +697,16 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / timing protocol only, no kernels and no GPU (gloo): CPU test of the "
                          "multi-rank path; the JSON carries value null")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (force-kernel roofline, debiased regime, the aldp22 backbone, "
+                         "whole-integrate_sde and small-batch legs, CPU baselines); the --no-* / --force-* options select "
+                         "among them.  Without it the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the walkers they computed (what pita_egnn_sampler_run hands its "
+                         "caller; several ranks: the all-gathered batch) to DIR/walkers.npy, float32")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline steps and nothing else
+        args.force_evals, args.no_debiased, args.no_e2e, args.no_small_batch, args.no_cpu_baseline = 0, True, True, True, True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -782,7 +809,7 @@ def main():
         Bd = B
         debiased = debiased_leg(pita_amd, net, cfg, dev, Bd, with_cpu=world == 1 and not args.no_cpu_baseline and n <= 13)
     ad2cat = None
-    if rank == 0 and world == 1 and args.config == "aldp22" and not args.force_last:
+    if args.full and rank == 0 and world == 1 and args.config == "aldp22" and not args.force_last:
         # the reference's alanine-dipeptide EGNN (egnn_dynamics_ad2_cat.yaml: hidden 64 x 5 layers, one-hot atom types) on
         # the matrix-pipe wide kernel, through the integrator's per-step path (fused EDM evaluation + pita_em_step)
         from pita_amd.egnn_dynamics_ad2_cat import EGNN_dynamics_AD2_cat
@@ -850,7 +877,20 @@ def main():
                       2 * mac * B / dt64 / (2500e12 if on_mfma else 78.65e12),
                   "finite": bool(torch.isfinite(xa).all())}
         del xa
-    run(0, W)  # warm-up (also builds the native handle)
+    # clock warm-up: >= 0.3 s of this kernel's launches on a COPY of the walkers (the timed walkers are not touched).  From a
+    # cold start the chip needs ~40 ms of sustained matrix work to reach the clock it then holds, and a
+    # short timed region (the driver's --steps 20 --warmup 5: 27 ms) would sit inside that ramp.  (In a --full run the
+    # secondary legs in front warm the chip as well.)
+    xs = x.clone()
+    run_on = lambda xw: net.sampler_run(xw, tab[:chunk], chunk, seed=seed, walker_offset=rank * B, step0=0, remove_mean=True)
+    run_on(xs)  # (also builds the native handle)
+    torch.cuda.synchronize()
+    t_spin = time.perf_counter()
+    while time.perf_counter() - t_spin < 0.3:
+        run_on(xs)
+        torch.cuda.synchronize()
+    del xs
+    run(0, W)  # warm-up
     gathered = torch.empty(world * B, D, device=dev) if world > 1 else None
     torch.cuda.synchronize()
     if world > 1:
@@ -885,6 +925,8 @@ def main():
         # for the slowest rank to arrive, which is what a rank loses to the collective)
         per_rank = rank_breakdown(world, gather64, wall, sum(launch_ms) * 1e-3, evs[n_launch].elapsed_time(ev_ag) * 1e-3)
     assert torch.isfinite(x).all(), "sampler produced non-finite walkers"
+    if args.dump_outputs and rank == 0:
+        dump_walkers(args.dump_outputs, gathered if world > 1 else x)
     e2e_ranks = None
     if world > 1 and not args.no_e2e:
         e2e_ranks = e2e_multi_rank(pita_amd, net, cfg, dev, B, world, NGRID, gather64)

@@ -227,3 +227,21 @@ def test_step_table_is_cached_by_value_not_by_object():
     n = len(si._STEP_TABLES)
     si.build_step_table(Odd(), gam, times, 1 / 40, 1.0, 1.0)
     assert len(si._STEP_TABLES) == n
+
+
+def test_bench_dump_walkers_keeps_small_batches_whole_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a batch within the byte budget is written whole as float32; a larger one as a fixed,
+    seeded sample of its rows in walker order, the same rows every time."""
+    import bench  # the repository root is on sys.path (tests/conftest.py)
+
+    x = torch.arange(100 * 39, dtype=torch.float64).reshape(100, 39)
+    bench.dump_walkers(str(tmp_path / "whole"), x)
+    a = np.load(tmp_path / "whole" / "walkers.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 39 * 4 + 5)
+    bench.dump_walkers(str(tmp_path / "s1"), x)
+    bench.dump_walkers(str(tmp_path / "s2"), x)
+    s1, s2 = np.load(tmp_path / "s1" / "walkers.npy"), np.load(tmp_path / "s2" / "walkers.npy")
+    assert s1.shape == (10, 39) and np.array_equal(s1, s2)
+    rows = s1[:, 0].astype(np.int64) // 39
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, x.float().numpy()[rows])

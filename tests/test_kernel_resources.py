@@ -13,11 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def _kernels(obj):
-    fb, co = "/tmp/_kr_test.fb", "/tmp/_kr_test.co"
+def _kernels(obj, tmp):
+    fb, co = os.path.join(tmp, "_kr_test.fb"), os.path.join(tmp, "_kr_test.co")
     # (an explicit output file: objcopy without one rewrites its input, and a touched object makes the next build() rebuild)
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, "/tmp/_kr_test.o"], check=True,
-                   capture_output=True)
+    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, os.path.join(tmp, "_kr_test.o")],
+                   check=True, capture_output=True)
     subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}", f"--output={co}",
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True, capture_output=True)
     txt = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
@@ -32,13 +32,13 @@ def _kernels(obj):
 
 @pytest.mark.skipif(not os.path.exists(f"{LLVM}/llvm-readelf") or shutil.which("c++filt") is None,
                     reason="needs the ROCm LLVM binutils")
-def test_register_and_scratch_budgets():
+def test_register_and_scratch_budgets(tmp_path):
     import pita_amd.build as build
 
     build.build(verbose=False)
     k = {}
     for f in ("egnn_kernel.o", "egnn_div_kernel.o", "energy_kernels.o"):
-        k.update(_kernels(os.path.join(ROOT, "pita_amd", "csrc", f)))
+        k.update(_kernels(os.path.join(ROOT, "pita_amd", "csrc", f), str(tmp_path)))
     # fused sampler, default precision, every instantiated system: two waves per SIMD (<= 256 registers in total), its
     # spill code stays outside the edge loop (140 B/lane for LJ13 today)
     for name in ("egnn_kernel<13, 3, 7, 4, 2, true, 2>", "egnn_kernel<4, 2, 8, 4, 2, true, 2>",
@@ -96,7 +96,7 @@ def test_packed_fp32_exposure_of_shipped_kernels():
 
 
 @pytest.mark.skipif(not os.path.exists(f"{LLVM}/llvm-objdump"), reason="needs the ROCm LLVM binutils")
-def test_issue_priorities_are_in_the_built_kernels():
+def test_issue_priorities_are_in_the_built_kernels(tmp_path):
     """Round 5: the fused sampler's three SiLUs per edge and the block-shared tangent kernel's operand split run at the lower
     issue priority (s_setprio; DESIGN 4.1 viii: -6 % / -4.5 %, bit-identical results).  The scalar instructions must be in
     the objects that ship: six per unrolled edge and column tile in the sampler, two per edge item in the tangent kernel."""
@@ -105,8 +105,9 @@ def test_issue_priorities_are_in_the_built_kernels():
     build.build(verbose=False)
     for obj, needle, least in (("egnn_kernel.o", "egnn_kernelILi13ELi3ELi7ELi4ELi2ELb1ELi2E", 18),
                                ("egnn_div_kernel.o", "egnn_div_tangent_shared_kernelILi13ELi3ELi2ELi8ELi2E", 2)):
-        _kernels(os.path.join(ROOT, "pita_amd", "csrc", obj))  # leaves the device code object in /tmp/_kr_test.co
-        asm = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "/tmp/_kr_test.co"], check=True, capture_output=True, text=True).stdout
+        _kernels(os.path.join(ROOT, "pita_amd", "csrc", obj), str(tmp_path))  # leaves the device code object in tmp_path
+        asm = subprocess.run([f"{LLVM}/llvm-objdump", "-d", str(tmp_path / "_kr_test.co")], check=True, capture_output=True,
+                             text=True).stdout
         start = asm.index(f"<_ZN4pita{len(needle.split('IL')[0])}{needle}")
         body = asm[start:asm.index("s_endpgm", start)]
         assert body.count("s_setprio") >= least, (obj, body.count("s_setprio"))

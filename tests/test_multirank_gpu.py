@@ -45,11 +45,12 @@ def test_two_ranks_reproduce_one_rank_bitwise():
 
 def test_bench_two_ranks_on_one_device():
     """`python bench.py --gpus 2` starts its own two ranks (before touching the GPU) and rank 0 reports n_gpus = 2 and
-    the whole-job rate; PITA_BENCH_ONE_DEVICE=1 puts both ranks on cuda:0 over gloo."""
+    the whole-job rate; PITA_BENCH_ONE_DEVICE=1 puts both ranks on cuda:0 over gloo.  --full: the per-rank whole
+    integrate_sde (`e2e`) is a secondary leg."""
     env = _env()
     env["PITA_BENCH_ONE_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--walkers", "1024", "--no-cpu-baseline", "--no-debiased", "--force-evals", "0",
+                        "--walkers", "1024", "--full", "--no-cpu-baseline", "--no-debiased", "--force-evals", "0",
                         "--resample-every", "1"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])

@@ -1,6 +1,6 @@
 """Host side of the C ABI under AddressSanitizer / UndefinedBehaviorSanitizer / LeakSanitizer: a CPU-only test (no kernel
-is launched).  Kept in its own file and listed in .gpurunignore: the GPU pool refuses any call whose snapshot contains a
-sanitizer build line (GPU sanitizers are not available there), and the GPU run does not need this file."""
+is launched).  Only the host code is instrumented: every compile or link line that names a sanitizer also carries
+-fno-gpu-sanitize, so no GPU sanitizer build (and no xnack+ code object) is ever made."""
 import os
 import subprocess
 
@@ -25,15 +25,17 @@ def test_host_glue_under_address_and_ub_sanitizers(tmp_path):
         out, _ = p.communicate()
         assert p.returncode == 0, f"{s}: {out[-2000:]}"
     lib = tmp_path / "libpita_hip_asan.so"
-    subprocess.check_call([_b.HIPCC, "-shared", "-fPIC", "-fsanitize=address,undefined", "-o", str(lib), *objs])
+    subprocess.check_call([_b.HIPCC, "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-o", str(lib),
+                           *objs])
     nm = subprocess.check_output(["nm", "-D", str(lib)], text=True)
     assert "__asan_init" in nm and "__ubsan_handle" in nm, "the host objects are not instrumented"
     exe = tmp_path / "abi_probe_sanitized"
     clang = os.path.join(os.path.dirname(os.path.realpath(_b.HIPCC)), "..", "lib", "llvm", "bin", "clang")
     if not os.path.exists(clang):
         clang = "/opt/rocm/lib/llvm/bin/clang"
-    subprocess.check_call([clang, "-std=c99", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "abi_probe_sanitized.c"),
+    subprocess.check_call([clang, "-std=c99", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+                           "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "abi_probe_sanitized.c"),
                            "-o", str(exe), "-L", str(tmp_path), "-lpita_hip_asan", f"-Wl,-rpath,{tmp_path}",
                            "-Wl,-rpath,/opt/rocm/lib"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")

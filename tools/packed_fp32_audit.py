@@ -12,6 +12,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
@@ -19,14 +20,15 @@ PK = re.compile(r"\bv_pk_(mul|add|fma)_f32\b")
 
 
 def disassemble(obj, tag="audit"):
-    fb, co = f"/tmp/_pk_{tag}.fb", f"/tmp/_pk_{tag}.co"
-    r = subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, f"/tmp/_pk_{tag}.o"],
-                       capture_output=True)
-    if r.returncode != 0:  # an object without device code (abi.hip)
-        return ""
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}", f"--output={co}",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True, capture_output=True)
-    return subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], check=True, capture_output=True, text=True).stdout
+    with tempfile.TemporaryDirectory() as tmp:  # private to this call: no clash with another user's or run's files
+        fb, co = os.path.join(tmp, f"_pk_{tag}.fb"), os.path.join(tmp, f"_pk_{tag}.co")
+        r = subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, os.path.join(tmp, f"_pk_{tag}.o")],
+                           capture_output=True)
+        if r.returncode != 0:  # an object without device code (abi.hip)
+            return ""
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}", f"--output={co}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True, capture_output=True)
+        return subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], check=True, capture_output=True, text=True).stdout
 
 
 def audit_object(obj):
