@@ -209,6 +209,12 @@ typedef struct {
   float gb_solute_dielectric, gb_solvent_dielectric;               /* OpenMM defaults 1.0, 78.5 */
   float gb_surface_area_factor;                                    /* 4 pi x 2.25936 kJ/mol/nm^2 = 28.3919551; 0 = no SA term */
 } pita_ff_config;
+/* Capacity: 2 <= n_atoms <= 256 (one thread per (walker, atom) in a 256-thread block), else PITA_EINVAL before any
+ * device call.  The handle carries one launch plan for both entry points: floor(256 / n_atoms) walkers per block, or
+ * fewer where the device's per-block LDS cannot hold the interaction tables (bonded terms, the dense pair table,
+ * per-atom lists) plus that many walkers' working set; where not even one walker fits, PITA_EUNSUPPORTED with the bytes
+ * needed and available.  A handle that exists is therefore taken by both pita_ff_logp_force and pita_ff_descent, and a
+ * walker's result does not depend on the plan. */
 int pita_ff_create(pita_ff_t** out, const pita_ff_config* cfg);
 int pita_ff_destroy(pita_ff_t* ff);
 int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, float* force /*nullable*/, int64_t B, void* stream);

@@ -101,7 +101,9 @@ class ForceFieldEnergy(BaseMoleculeEnergy):
                  gb_solvent_dielectric=78.5, gb_surface_area_factor=28.3919551, **kwargs):
         """tables: dict of numpy arrays / tensors: bond_idx[nb,2], bond_par[nb,2], angle_idx[na,3], angle_par[na,2],
         tors_idx[nt,4], tors_par[nt,3], charge[n], sigma[n], epsilon[n], exc_idx[ne,2], exc_par[ne,3]; optional
-        gb_radius[n], gb_scale[n] switch the GB-OBC1 implicit solvent on (OpenMM GBSAOBCForce parameters)."""
+        gb_radius[n], gb_scale[n] switch the GB-OBC1 implicit solvent on (OpenMM GBSAOBCForce parameters).
+        Up to 256 atoms (alanine di-, tri- and tetra-peptide and beyond): the kernel handle takes as many walkers per
+        block as the device's LDS holds with these tables, the same for ``__call__`` and ``fused_descent``."""
         assert spatial_dim == 3
         super().__init__(dimensionality=3 * n_particles, n_particles=n_particles, spatial_dim=3, data_path=None,
                          device=device, is_molecule=is_molecule, temperature=temperature, should_normalize=False,

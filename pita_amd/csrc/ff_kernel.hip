@@ -9,15 +9,16 @@
 // oracle's restatement of the same forms (autograd forces) on synthetic topologies.
 //
 // Mapping: one thread = one (walker, atom), floor(256/n) walkers per 256-thread block (so even the 4 096 walkers per
-// GPU of BASELINE config C4 put a wave on every SIMD); coordinates and tables live in LDS; loads and stores of
-// x / force are contiguous spans.  ~14 kflop (+ ~60 kflop with GB-OBC1) and 536 B per walker-eval for a 22-atom
-// peptide: compute- rather than bandwidth-bound.
+// GPU of BASELINE config C4 put a wave on every SIMD) unless the LDS cannot hold that many (launch plan, pita_ff_create);
+// coordinates and tables live in LDS; loads and stores of x / force are contiguous spans.  ~14 kflop (+ ~60 kflop with
+// GB-OBC1) and 536 B per walker-eval for a 22-atom peptide: compute- rather than bandwidth-bound.
 #include "common.h"
 
 namespace pita {
 
 struct FfParams {
   int n, nb, na, nt, np;
+  int wpb;               // walkers per block: the launch plan of pita_ff_create, the same for both entry points
   // tables (inside `blob`): bond_idx[nb][2], bond_par[nb][2], angle_idx[na][3], angle_par[na][2], tors_idx[nt][4],
   // tors_par[nt][3], pair_idx[np][2], pair_par[np][4] = (ONE_4PI_EPS0*qq, sigma, 4*eps, is_exception)
   float length_scale, inv_kT, cutoff, krf, crf;
@@ -51,7 +52,7 @@ constexpr int FF_THREADS = 256;
 template <bool DESCENT>
 __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
   extern __shared__ float sm[];
-  const int n = p.n, D = 3 * n, WPB = FF_THREADS / n;
+  const int n = p.n, D = 3 * n, WPB = p.wpb;
   // interaction tables: LDS-resident for the whole (persistent) block
   unsigned* tb = reinterpret_cast<unsigned*>(sm);
   for (int i = threadIdx.x; i < p.blob_words; i += FF_THREADS) tb[i] = p.blob[i];
@@ -352,15 +353,17 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
 struct pita_ff {
   pita::FfParams p{};
   void* d_all = nullptr;
+  size_t lds_logp = 0, lds_descent = 0;  // dynamic LDS bytes per block of the two entry points at p.wpb walkers
 };
 
 using namespace pita;
 
 extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
   PITA_REQUIRE(out && c, "pita_ff_create: null argument");
-  PITA_REQUIRE(c->n_atoms >= 2 && c->n_atoms <= 40, "pita_ff_create: n_atoms must be in [2,40]");
+  PITA_REQUIRE(c->n_atoms >= 2 && c->n_atoms <= FF_THREADS, "pita_ff_create: n_atoms must be in [2,%d]", FF_THREADS);
   PITA_REQUIRE(c->charge && c->sigma && c->epsilon, "pita_ff_create: per-atom nonbonded parameters missing");
   PITA_REQUIRE(c->kT > 0.f && c->length_scale > 0.f, "pita_ff_create: kT and length_scale must be > 0");
+  PITA_REQUIRE(!c->use_cutoff || c->cutoff > 0.f, "pita_ff_create: cutoff must be > 0");
   PITA_REQUIRE((c->n_bonds == 0 || (c->bond_idx && c->bond_par)) && (c->n_angles == 0 || (c->angle_idx && c->angle_par)) &&
                    (c->n_torsions == 0 || (c->tors_idx && c->tors_par)) && (c->n_exceptions == 0 || (c->exc_idx && c->exc_par)),
                "pita_ff_create: table pointer missing");
@@ -444,7 +447,32 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     tcs[2 * t + 1] = (float)sin((double)c->tors_par[3 * t + 1]);
   }
   const size_t total = b_bi + b_bp + b_ai + b_ap + b_ti + b_tp + b_tc + b_pi + b_pp + b_gb + b_co + b_ce + 16 * 12;  // each table padded to 16 B
+  // Launch plan, shared by both entry points: floor(256/n) walkers per block where the LDS holds them, fewer where it
+  // does not.  Sized for the descent kernel (the larger footprint), so a handle that exists is taken by both.
+  auto pad16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+  const size_t blob_bytes = pad16(b_bi) + pad16(b_bp) + pad16(b_ai) + pad16(b_ap) + pad16(b_ti) + pad16(b_tp) + pad16(b_tc) +
+                            pad16(b_pi) + pad16(b_pp) + pad16(b_gb) + pad16(b_co) + pad16(b_ce);
+  // per walker: xs, gs [3n]; es, br, bw [n]; tg [3 n_slots]; descent adds xu, vv [3n] (layout of ff_kernel)
+  const size_t walker_logp = sizeof(float) * ((size_t)9 * n + (size_t)3 * n_ent);
+  const size_t walker_descent = walker_logp + sizeof(float) * (size_t)6 * n;
+  int dev = 0, lds_max = 0, lds_optin = 0;
+  hipError_t qe = hipGetDevice(&dev);
+  if (qe == hipSuccess) qe = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+  if (qe == hipSuccess && hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess &&
+      lds_optin > lds_max)
+    lds_max = lds_optin;
+  int wpb = FF_THREADS / n;
+  while (wpb > 0 && blob_bytes + (size_t)wpb * walker_descent > (size_t)lds_max) --wpb;
+  if (qe != hipSuccess || wpb == 0) {
+    delete[] pidx; delete[] ppar; delete[] gpar; delete[] csr_off; delete[] csr_ent; delete[] tcs;
+    if (qe != hipSuccess) return fail(PITA_EHIP, "pita_ff_create: LDS limit query failed: %s", hipGetErrorString(qe));
+    return fail(PITA_EUNSUPPORTED,
+                "pita_ff_create: one walker needs %zu B of LDS per block (%zu B of interaction tables), the device allows %d B",
+                blob_bytes + walker_descent, blob_bytes, lds_max);
+  }
   pita_ff* ff = new pita_ff();
+  ff->lds_logp = blob_bytes + (size_t)wpb * walker_logp;
+  ff->lds_descent = blob_bytes + (size_t)wpb * walker_descent;
   hipError_t e = hipMalloc(&ff->d_all, total);
   char* base = static_cast<char*>(ff->d_all);
   size_t off = 0;
@@ -478,7 +506,7 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     delete ff;
     return fail(PITA_EHIP, "pita_ff_create: device upload failed: %s", hipGetErrorString(e));
   }
-  p.n = n; p.nb = c->n_bonds; p.na = c->n_angles; p.nt = c->n_torsions; p.np = np;
+  p.n = n; p.nb = c->n_bonds; p.na = c->n_angles; p.nt = c->n_torsions; p.np = np; p.wpb = wpb;
   p.length_scale = c->length_scale; p.inv_kT = 1.0f / c->kT;
   p.use_cutoff = c->use_cutoff; p.cutoff = c->cutoff;
   p.gb = gb ? 1 : 0;
@@ -488,7 +516,6 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     p.gb_probe = 0.14f;
   }
   if (c->use_cutoff) {
-    PITA_REQUIRE(c->cutoff > 0.f, "pita_ff_create: cutoff must be > 0");
     const float er = c->rf_dielectric;
     p.krf = (1.0f / (c->cutoff * c->cutoff * c->cutoff)) * (er - 1.0f) / (2.0f * er + 1.0f);
     p.crf = (1.0f / c->cutoff) * (3.0f * er) / (2.0f * er + 1.0f);
@@ -510,12 +537,11 @@ extern "C" int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, fl
   PITA_REQUIRE(x && logp, "pita_ff_logp_force: null argument");
   FfParams p = ff->p;
   p.x = x; p.logp = logp; p.force = force; p.B = B;
-  const int WPB = FF_THREADS / p.n;
-  const size_t lds = sizeof(float) * ((size_t)p.blob_words + (size_t)WPB * (2 * 3 * p.n + 3 * p.n + 3 * (2 * p.nb + 3 * p.na + 4 * p.nt)));
-  PITA_REQUIRE(lds <= 64 * 1024, "pita_ff_logp_force: interaction tables do not fit in LDS");
-  const long long nblk = (B + WPB - 1) / WPB;
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_kernel<false>), ff->lds_logp));
+  const long long nblk = (B + p.wpb - 1) / p.wpb;
   const long long cap = 256LL * 8;  // persistent blocks: the tables are staged once per block
-  hipLaunchKernelGGL(ff_kernel<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ff_kernel<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), ff->lds_logp,
+                     (hipStream_t)stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -529,12 +555,11 @@ extern "C" int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise, int6
   FfParams p = ff->p;
   p.xio = x; p.noise = noise; p.B = B; p.steps = n_steps; p.dt = dt; p.noise_scale = noise_scale; p.sqrt_dt = sqrt_dt;
   p.seed = seed; p.walker_offset = walker_offset; p.step0 = step0; p.remove_mean = remove_mean;
-  const int WPB = FF_THREADS / p.n;
-  const size_t lds = sizeof(float) * ((size_t)p.blob_words + (size_t)WPB * (4 * 3 * p.n + 3 * p.n + 3 * (2 * p.nb + 3 * p.na + 4 * p.nt)));
-  PITA_REQUIRE(lds <= 64 * 1024, "pita_ff_descent: interaction tables do not fit in LDS");
-  const long long nblk = (B + WPB - 1) / WPB;
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_kernel<true>), ff->lds_descent));
+  const long long nblk = (B + p.wpb - 1) / p.wpb;
   const long long cap = 256LL * 8;
-  hipLaunchKernelGGL(ff_kernel<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ff_kernel<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), ff->lds_descent,
+                     (hipStream_t)stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
