@@ -71,6 +71,26 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes) {
   return e;
 }
 
+// A handle's scratch buffer grown on demand to at least `bytes` (plus `tail` bytes behind them that the size does not
+// count): the stream is drained first (an earlier launch may still use the old buffer), then the buffer is freed and
+// allocated anew and its size recorded.  On failure the buffer is null and its size 0; the error is returned.
+template <class T>
+inline hipError_t grow_scratch(T*& buf, size_t& size, size_t bytes, hipStream_t stream, size_t tail = 0) {
+  if (bytes <= size) return hipSuccess;
+  hipError_t e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return e;
+  (void)hipFree(buf);
+  buf = nullptr;
+  size = 0;
+  e = hipMalloc(&buf, bytes + tail);
+  if (e != hipSuccess) {
+    buf = nullptr;
+    return e;
+  }
+  size = bytes;
+  return hipSuccess;
+}
+
 // ---- device math with explicit accuracy choices
 // exp2/rcp map to single v_exp_f32 / v_rcp_f32 (about 1 ulp); used where the reference applies
 // sigmoid-family activations (relative error ~1e-7, no cancellation).
@@ -147,3 +167,17 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t walker, 
 }
 
 }  // namespace pita
+
+// makes `device` current for the lifetime of the guard (no-op when it already is)
+struct PitaDeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit PitaDeviceGuard(int device) {
+    if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
+  }
+  ~PitaDeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+  PitaDeviceGuard(const PitaDeviceGuard&) = delete;
+  PitaDeviceGuard& operator=(const PitaDeviceGuard&) = delete;
+};

@@ -355,20 +355,6 @@ __device__ __forceinline__ float tanh_select(float v) {
 
 }  // namespace pita
 
-// makes `device` current for the lifetime of the guard (no-op when it already is)
-struct PitaDeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit PitaDeviceGuard(int device) {
-    if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
-  }
-  ~PitaDeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-  PitaDeviceGuard(const PitaDeviceGuard&) = delete;
-  PitaDeviceGuard& operator=(const PitaDeviceGuard&) = delete;
-};
-
 struct pita_egnn {
   pita_egnn_config cfg;
   unsigned* d_mats16 = nullptr;  // [L][M_COUNT][3][2][64][4]  bf16-split fragments

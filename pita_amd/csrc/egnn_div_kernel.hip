@@ -2169,76 +2169,32 @@ __global__ void __launch_bounds__(NW * 64, 1) egnn_div_tangent_shared_kernel(Div
   flush();
 }
 
-struct DivShape {
+// One row per particle system holds all its divergence kernels.  Except the block-shared tangent kernel, they share the
+// row's mapping -- groups of G walkers, `waves` waves per block, at most one block per CU (one wave per SIMD) -- which is
+// what lets the tangent-only kernels read the primal cache the first launch of a trace wrote (it is indexed by wave and
+// group).  The row is built from its template arguments, so the kernels cannot disagree on G or `waves`.
+struct DivKernel {
+  void (*kernel)(DivParams) = nullptr;
+  size_t (*lds_bytes)(int) = nullptr;
+  int waves = 0, K = 0;          // waves per block, directions per wave and launch
+  bool (*fits)(int) = nullptr;   // block-shared tangent kernel: the network depth fits its LDS budget and piece table
+};
+struct DivSystem {
   int n, dim, G, waves, K;
-  void (*kernel)(DivParams);
-  void (*fast)(DivParams);
-  size_t (*lds_bytes)(int);
-  int occ = 1;  // blocks per CU the fast kernel is built for (grid cap)
+  DivKernel bf16x3;            // every precision; the repair pass behind the f16 kernel (accepts any ndir <= K)
+  DivKernel f16;               // precision 2: marks the walkers whose terms were not finite, for the repair pass
+  DivKernel writer;            // nullable: cache writer, the first launch of a trace streamed by the block-shared kernel
+  DivKernel shared, owned;     // nullable: tangent-only kernels (primal cache), block-shared and wave-owned
+  size_t (*group_f)(int);      // cache floats per walker group
 };
 template <int N, int DIM, int G, int WAVES, int K, int DAL>
 static size_t div_lds_bytes_of(int L) { return DivCfg<N, DIM, G, WAVES, K, DAL>::lds_bytes(L); }
-#define PITA_DIV_SHAPE(N, DIM, G, WAVES, K) \
-  DivShape { N, DIM, G, WAVES, K, egnn_div_kernel<N, DIM, G, WAVES, K>, egnn_div_fast_kernel<N, DIM, G, WAVES, K, 1>, \
-             div_lds_bytes_of<N, DIM, G, WAVES, K, 1> }
-// fast kernel only, Wa dh_i in registers (frees LDS for a fourth direction); the repair kernel is the K-direction
-// kernel of kDivShapes, which accepts any ndir <= its own K -- so these are used for the fast launch only
-#define PITA_DIV_FAST_SHAPE(N, DIM, G, WAVES, K) \
-  DivShape { N, DIM, G, WAVES, K, nullptr, egnn_div_fast_kernel<N, DIM, G, WAVES, K, 0>, \
-             div_lds_bytes_of<N, DIM, G, WAVES, K, 0> }
-static const DivShape kDivShapes[] = {
-    PITA_DIV_SHAPE(4, 2, 8, 4, 3),
-    PITA_DIV_SHAPE(13, 3, 2, 4, 3),
-    PITA_DIV_SHAPE(22, 3, 1, 4, 3),
-    PITA_DIV_SHAPE(55, 3, 1, 4, 1),
-};
-// measured for LJ13 at 65 536 walkers, all 39 directions: K = 2: 117.9 ms, K = 3: 100.6 ms (93.3 ms with Wa dh_i parked
-// in LDS), K = 4: 102.8 ms (more register shuffling; no longer fits in LDS), 39 single-direction JVP launches: 126 ms.
-// PITA_DIV_K selects an alternative for experiments.
-static const DivShape kDivAlt[] = {PITA_DIV_SHAPE(13, 3, 2, 4, 2)};
-// cache writers for the block-shared tangent kernel: the first launch of a trace carries NO direction (round 4; a
-// direction costs 0.9 ms in this one-wave-per-SIMD launch and 0.17 ms in a tangent-only launch, which take 16 each: 0 + 13
-// + 13 + 13 for LJ13; rounds 2-3: 1 + 13 + 13 + 12) and marks out-of-range walkers by their primal
-// (measured with two blocks per CU, i.e. two waves per SIMD at 256 registers: 976 B/lane of scratch, the launch takes
-// 14 ms instead of 5 -- the primal's adjoint factors plus one tangent chain need the 492 registers it uses)
-#define PITA_DIV_WRITER_SHAPE(N, DIM, G, WAVES) \
-  DivShape { N, DIM, G, WAVES, 0, nullptr, egnn_div_fast_kernel<N, DIM, G, WAVES, 0, 0, 1>, \
-             div_lds_bytes_of<N, DIM, G, WAVES, 0, 0>, 1 }
-static const DivShape kDivWriters[] = {PITA_DIV_WRITER_SHAPE(13, 3, 2, 4), PITA_DIV_WRITER_SHAPE(22, 3, 1, 4)};
-static const DivShape* find_div_writer(int n, int dim) {
-  static const bool off = getenv("PITA_DIV_NOWRITER") != nullptr;  // development aid
-  if (off) return nullptr;
-  for (const auto& c : kDivWriters)
-    if (c.n == n && c.dim == dim) return &c;
-  return nullptr;
-}
-static const DivShape* find_div_shape(int n, int dim) {
-  static const int altk = getenv("PITA_DIV_K") ? atoi(getenv("PITA_DIV_K")) : 0;
-  if (altk)
-    for (const auto& c : kDivAlt)
-      if (c.n == n && c.dim == dim && c.K == altk) return &c;
-  for (const auto& c : kDivShapes)
-    if (c.n == n && c.dim == dim) return &c;
-  return nullptr;
-}
-// f16 kernel with more directions per launch than the bf16x3 kernel's LDS budget allows (Wa dh_i in registers);
-// PITA_DIV_FAST_K=0 falls back to the bf16x3 kernel's K (development aid)
-// tangent-only kernels (primal cache): same G / WAVES as the fast kernel of the particle system
-struct DivTanShape {
-  int n, dim, G, waves, K;
-  int shared;              // 1: block-shared kernel (`waves` waves on one walker group, waves x K directions per launch)
-  void (*kernel)(DivParams);
-  size_t (*lds_bytes)(int);
-  size_t (*group_f)(int);  // cache floats per walker group
-  bool (*fits)(int);       // block-shared kernel: the network depth fits its LDS budget and piece table
-};
 template <int N, int DIM, int G, int WAVES, int K>
 static size_t divtan_lds_of(int L) { return DivTanCfg<N, DIM, G, WAVES, K>::lds_bytes(L); }
+template <int N, int DIM, int G, int NW, int K>
+static size_t divshr_lds_of(int L) { return DivShrCfg<N, DIM, G, NW, K>::lds_bytes(L); }
 template <int N, int DIM, int G>
 static size_t divcache_group_f(int L) { return DivCache<N, DIM, (G * N + 31) / 32>::group_f(L); }
-#define PITA_DIVTAN_SHAPE(N, DIM, G, WAVES, K) \
-  DivTanShape { N, DIM, G, WAVES, K, 0, egnn_div_tangent_kernel<N, DIM, G, WAVES, K>, divtan_lds_of<N, DIM, G, WAVES, K>, \
-                divcache_group_f<N, DIM, G>, nullptr }
 // items of one group's sweep (as the kernel's piece table lays them out) against the table's capacity
 template <int N, int DIM, int G, int NW, int K>
 static bool divshr_fits(int L) {
@@ -2252,64 +2208,122 @@ static bool divshr_fits(int L) {
   }
   return items * (C::COMPACT ? 2 : SHR_S) <= C::MAX_P;
 }
-template <int N, int DIM, int G, int NW, int K>
-static size_t divshr_lds_of(int L) { return DivShrCfg<N, DIM, G, NW, K>::lds_bytes(L); }
-#define PITA_DIVSHR_SHAPE(N, DIM, G, NW, K) \
-  DivTanShape { N, DIM, G, NW, K, 1, egnn_div_tangent_shared_kernel<N, DIM, G, NW, K>, divshr_lds_of<N, DIM, G, NW, K>, \
-                divcache_group_f<N, DIM, G>, divshr_fits<N, DIM, G, NW, K> }
-// LJ13, all 39 directions at 65 536 walkers (first launch 5.7 ms incl. the 12 GB cache write): K = 3: 34.9 ms, K = 4:
-// 32.9 ms (9 launches of 3.0 ms = 4 TB/s of cache reads), K = 5: 39.6 ms, K = 6: 44.0 ms (528 / 860 B/lane of scratch);
-// without the cache (13 fast launches): 59-62 ms.  Also measured: the four waves of a block sharing ONE walker group with
-// K = 2 directions each at two waves per SIMD, every wave streaming the same records and counting on the L2 for the
-// repeats: 46.4 ms -- each wave's stream goes to HBM (5 launches of 8 ms = 4 x 12 GB at 5.5 TB/s); sharing would have to
-// be explicit (records staged once per block in LDS).
+// WRITER: the system has a cache writer; SHR_NW / SHR_K: waves and directions per wave of the block-shared tangent
+// kernel, OWN_K: directions of the wave-owned one (0: none)
+template <int N, int DIM, int G, int WAVES, int K, bool WRITER, int SHR_NW, int SHR_K, int OWN_K>
+static DivSystem div_system() {
+  DivSystem s{N, DIM, G, WAVES, K,
+              {egnn_div_kernel<N, DIM, G, WAVES, K>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K},
+              {egnn_div_fast_kernel<N, DIM, G, WAVES, K, 1>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K},
+              {}, {}, {}, divcache_group_f<N, DIM, G>};
+  if constexpr (WRITER)
+    s.writer = {egnn_div_fast_kernel<N, DIM, G, WAVES, 0, 0, 1>, div_lds_bytes_of<N, DIM, G, WAVES, 0, 0>, WAVES, 0};
+  if constexpr (SHR_K > 0)
+    s.shared = {egnn_div_tangent_shared_kernel<N, DIM, G, SHR_NW, SHR_K>, divshr_lds_of<N, DIM, G, SHR_NW, SHR_K>, SHR_NW,
+                SHR_K, divshr_fits<N, DIM, G, SHR_NW, SHR_K>};
+  if constexpr (OWN_K > 0)
+    s.owned = {egnn_div_tangent_kernel<N, DIM, G, WAVES, OWN_K>, divtan_lds_of<N, DIM, G, WAVES, OWN_K>, WAVES, OWN_K};
+  return s;
+}
+// K (directions per launch of the bf16x3 / f16 kernels), measured for LJ13 at 65 536 walkers, all 39 directions: K = 2:
+// 117.9 ms, K = 3: 100.6 ms (93.3 ms with Wa dh_i parked in LDS), K = 4: 102.8 ms (more register shuffling; no longer
+// fits in LDS), 39 single-direction JVP launches: 126 ms.  The f16 kernel with K = 4 and Wa dh_i in registers: 65.3 ms
+// against 61.9 ms with K = 3 (800 B/lane of scratch: the fourth direction's state no longer fits the 512 registers).
+//
+// Cache writers: the first launch of a trace carries NO direction (round 4; a direction costs 0.9 ms in this
+// one-wave-per-SIMD launch and 0.17 ms in a tangent-only launch, which take 16 each: 0 + 13 + 13 + 13 for LJ13; rounds
+// 2-3: 1 + 13 + 13 + 12) and marks out-of-range walkers by their primal (measured with two blocks per CU, i.e. two waves
+// per SIMD at 256 registers: 976 B/lane of scratch, the launch takes 14 ms instead of 5 -- the primal's adjoint factors
+// plus one tangent chain need the 492 registers it uses).
+//
+// Tangent-only kernels, LJ13, all 39 directions at 65 536 walkers (first launch 5.7 ms incl. the 12 GB cache write):
+// wave-owned K = 3: 34.9 ms, K = 4: 32.9 ms (9 launches of 3.0 ms = 4 TB/s of cache reads), K = 5: 39.6 ms, K = 6: 44.0 ms
+// (528 / 860 B/lane of scratch); without the cache (13 fast launches): 59-62 ms.  Also measured: the four waves of a
+// block sharing ONE walker group with K = 2 directions each at two waves per SIMD, every wave streaming the same records
+// and counting on the L2 for the repeats: 46.4 ms -- each wave's stream goes to HBM (5 launches of 8 ms = 4 x 12 GB at
+// 5.5 TB/s); sharing would have to be explicit (records staged once per block in LDS).
 // Block-shared kernel (LDS-DMA ring), same batch: (8 waves, K = 2) 26.3 ms, (12 waves, K = 1) 25.6-26.3 ms, (6 waves, K = 2)
 // 28.5 ms: three launches of 6.3-6.8 ms that stream the cache once per 16 / 12 directions.  Per launch the LDS pipe is
 // busy ~3 ms (every wave reads the records it shares: 24 KB per direction and middle-layer edge), the vector ALUs ~2 ms,
 // the scalar ALU (one per CU: the ring bookkeeping of all waves) ~1 ms, the stream alone takes 2.1-2.5 ms; the waves
 // run in lock step (one barrier per item), so these overlap only partly.
-static const DivTanShape kDivTan[] = {
-    PITA_DIVTAN_SHAPE(4, 2, 8, 4, 5),
-    PITA_DIVSHR_SHAPE(13, 3, 2, 8, 2),
-    PITA_DIVSHR_SHAPE(22, 3, 1, 8, 2),
-    PITA_DIVSHR_SHAPE(55, 3, 1, 8, 1),
-};
-// wave-owned kernels for the systems above that default to the block-shared one (networks deeper than its LDS budget
-// is sized for; PITA_DIV_TAN_ALT=1 selects them for A/B runs), then experiments (PITA_DIV_TAN_ALT=<index + 1>)
-constexpr int kDivTanOwned = 3;  // the first kDivTanOwned entries are the wave-owned fallbacks
-static const DivTanShape kDivTanAlt[] = {PITA_DIVTAN_SHAPE(13, 3, 2, 4, 4), PITA_DIVTAN_SHAPE(22, 3, 1, 4, 4),
-                                         PITA_DIVTAN_SHAPE(55, 3, 1, 4, 3), PITA_DIVSHR_SHAPE(13, 3, 2, 12, 1)};
 // (Round 6, measured and removed: seven / six waves per block -- every wave's tangent tables are 10.75 KB of LDS, so fewer waves
 // leave FOUR ring slots instead of three -- LJ55 trace 610 -> 855 / 903 ms at 32 768 walkers, LJ13 18.4 -> 25.0 ms with seven
 // waves: the launches are bound by the waves' own work, not by the ring's depth; profiles/r06_tangent_waves_per_block_ab.txt.)
-static const DivTanShape* find_div_tan_shape(int n, int dim, int n_layers) {
-  static const bool off = getenv("PITA_DIV_NOCACHE") != nullptr;  // development aid: A/B against the cache-free path
-  if (off) return nullptr;
-  static const int alt = getenv("PITA_DIV_TAN_ALT") ? atoi(getenv("PITA_DIV_TAN_ALT")) : 0;
-  const int nalt = (int)(sizeof(kDivTanAlt) / sizeof(kDivTanAlt[0]));
-  if (alt == 1) {
-    for (int i = 0; i < kDivTanOwned; ++i)
-      if (kDivTanAlt[i].n == n && kDivTanAlt[i].dim == dim) return &kDivTanAlt[i];
-  } else if (alt > kDivTanOwned && alt <= nalt) {
-    const auto& c = kDivTanAlt[alt - 1];
-    if (c.n == n && c.dim == dim && (!c.shared || c.fits(n_layers))) return &c;
+// The wave-owned kernels of 13, 22 and 55 particles serve the networks too deep for the block-shared kernel's LDS budget.
+static const DivSystem kDivSystems[] = {
+    //         N   DIM G  WAVES K  writer shared NW, K  owned K
+    div_system<4,  2,  8, 4,    3, false, 0,     0,     5>(),
+    div_system<13, 3,  2, 4,    3, true,  8,     2,     4>(),
+    div_system<22, 3,  1, 4,    3, true,  8,     2,     4>(),
+    div_system<55, 3,  1, 4,    1, false, 8,     1,     3>(),
+};
+
+// What the entry points do with a handle.  A full trace (pita_egnn_jacobian_trace) of a precision-2 handle whose system
+// has a tangent-only kernel for this depth takes the primal-cache path: ONE launch with the primal (`first`, first->K
+// directions) writes the cache, tangent-only launches stream it.  Every other trace takes launches of K directions.
+struct DivPlan {
+  const DivSystem* sys = nullptr;     // null: no kernel for this particle system
+  bool f16 = false;                   // the f16 kernel, then the bf16x3 kernel repairs the walkers it marked
+  const DivKernel* first = nullptr;   // primal-cache path: the launch that writes the cache; null: no cache
+  const DivKernel* tangent = nullptr;
+};
+static DivPlan div_plan(const pita_egnn* net) {
+  DivPlan pl;
+  for (const auto& s : kDivSystems)
+    if (s.n == net->cfg.n_particles && s.dim == net->cfg.n_dim) pl.sys = &s;
+  if (!pl.sys) return pl;
+  const DivSystem& s = *pl.sys;
+  pl.f16 = net->cfg.precision == 2;
+  if (!pl.f16 || s.n * s.dim <= s.K) return pl;
+  if (s.shared.kernel && s.shared.fits(net->cfg.n_layers)) {
+    pl.tangent = &s.shared;
+    pl.first = s.writer.kernel ? &s.writer : &s.f16;
+  } else if (s.owned.kernel) {
+    pl.tangent = &s.owned;
+    pl.first = &s.f16;
   }
-  for (const auto& c : kDivTan)
-    if (c.n == n && c.dim == dim) {
-      if (!c.shared || c.fits(n_layers)) return &c;
-      for (int i = 0; i < kDivTanOwned; ++i)
-        if (kDivTanAlt[i].n == n && kDivTanAlt[i].dim == dim) return &kDivTanAlt[i];
-      return nullptr;
-    }
-  return nullptr;
+  return pl;
 }
 
-// measured: K = 4 for LJ13 (PITA_DIV_FAST_SHAPE(13, 3, 2, 4, 4)): 65.3 ms for the 39 directions against 61.9 ms with K = 3
-// (800 B/lane of scratch: the fourth direction's state no longer fits the 512 registers) -- not instantiated
-static const DivShape* find_div_fast_shape(int n, int dim) { return find_div_shape(n, dim); }
-static bool div_fast_enabled(const pita_egnn* net) {
-  static const bool force_slow = getenv("PITA_DIV_SLOW") != nullptr;  // development aid: A/B against the bf16x3 kernel
-  return net->cfg.precision == 2 && !force_slow;
+// launch geometry over B walkers (all kernels of the row but the block-shared one): `waves` waves in all, each owning
+// groups_per_wave consecutive groups of G walkers
+struct DivGrid {
+  long long grid, waves, groups_per_wave;
+};
+static DivGrid div_grid(const pita_egnn* net, const DivSystem& s, long long B) {
+  const long long ngroups = (B + s.G - 1) / s.G;
+  const long long want = (ngroups + s.waves - 1) / s.waves;
+  const long long grid = want < net->n_cu ? want : net->n_cu;
+  const long long waves = grid * s.waves;
+  const long long quota = (B + waves - 1) / waves;
+  return {grid, waves, (quota + s.G - 1) / s.G};
+}
+
+static DivParams div_params(const pita_egnn* net) {
+  DivParams p{};
+  p.mats16 = net->d_mats16; p.mats16h = net->d_mats16h; p.vecs = net->d_vecs; p.vecs_h = net->d_vecs_h;
+  p.vecs_div = net->d_vecs_div;
+  p.n_layers = net->cfg.n_layers; p.in_nf = net->cfg.in_node_nf;
+  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.feature_layout = net->cfg.feature_layout;
+  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
+  return p;
+}
+
+static int div_launch(const DivKernel& k, long long grid, const DivParams& p, hipStream_t st) {
+  const size_t lds = k.lds_bytes(p.n_layers);
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(k.kernel), lds));
+  hipLaunchKernelGGL(k.kernel, dim3((unsigned)grid), dim3(k.waves * 64), lds, st, p);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// marks [B] + the flag word behind them (DivParams::bad_flag), zeroed when the buffer is allocated
+static int ensure_marks(pita_egnn_t* net, size_t B, hipStream_t st) {
+  if (sizeof(int) * B <= net->mark_bytes) return PITA_OK;
+  PITA_HIP_CHECK(grow_scratch(net->d_mark, net->mark_bytes, sizeof(int) * B, st, 64));
+  PITA_HIP_CHECK(hipMemsetAsync(net->d_mark + B, 0, 64, st));
+  return PITA_OK;
 }
 
 }  // namespace pita
@@ -2318,9 +2332,8 @@ using namespace pita;
 
 extern "C" int pita_egnn_div_directions(const pita_egnn_t* net) {
   if (!net) return PITA_EINVAL;
-  const DivShape* s = div_fast_enabled(net) ? find_div_fast_shape(net->cfg.n_particles, net->cfg.n_dim)
-                                            : find_div_shape(net->cfg.n_particles, net->cfg.n_dim);
-  return s ? s->K : PITA_EUNSUPPORTED;
+  const DivPlan pl = div_plan(net);
+  return pl.sys ? pl.sys->K : PITA_EUNSUPPORTED;
 }
 
 // Matrix-core wave-instructions per walker for one FULL trace (all D directions) on the path pita_egnn_jacobian_trace takes
@@ -2330,21 +2343,14 @@ extern "C" int pita_egnn_div_directions(const pita_egnn_t* net) {
 // per edge; per direction 6 x (Wb, Wa, Wn1a) from the second layer on and 6 x (Wn1b, Wn2) in every layer but the last.
 extern "C" int pita_egnn_div_work(const pita_egnn_t* net, double* mfma16_per_walker, double* mfma32_per_walker) {
   PITA_REQUIRE(net && mfma16_per_walker && mfma32_per_walker, "pita_egnn_div_work: null argument");
-  const DivShape* s = find_div_shape(net->cfg.n_particles, net->cfg.n_dim);
-  if (!s) return fail(PITA_EUNSUPPORTED, "pita_egnn_div_work: no kernel for this particle system");
-  const int N = s->n, L = net->cfg.n_layers, D = s->n * s->dim;
-  int K = s->K;
-  {  // the cached path's first launch may carry fewer directions (cache writer)
-    const DivTanShape* ts0 = div_fast_enabled(net) ? find_div_tan_shape(N, s->dim, L) : nullptr;
-    const DivShape* wr = (ts0 && ts0->shared) ? find_div_writer(N, s->dim) : nullptr;
-    if (wr && wr->G == s->G && wr->waves == s->waves && D > s->K) K = wr->K;
-  }
-  double launches = K > 0 ? (D + K - 1) / K : 0;
-  const double tiles_per_walker = (double)((s->G * N + 31) / 32) / s->G;
+  const DivPlan pl = div_plan(net);
+  if (!pl.sys) return fail(PITA_EUNSUPPORTED, "pita_egnn_div_work: no kernel for this particle system");
+  const DivSystem& s = *pl.sys;
+  const int N = s.n, L = net->cfg.n_layers, D = s.n * s.dim;
+  const int K = pl.first ? pl.first->K : s.K;  // directions of a launch with the primal
+  const double tiles_per_walker = (double)((s.G * N + 31) / 32) / s.G;
   double m16 = 0, m32 = 0, t16 = 0, t32 = 0;  // per tile: one K-direction launch with primal; one tangent-only direction
-  const bool fast = div_fast_enabled(net);
-  const bool cached = fast && find_div_tan_shape(N, s->dim, L) != nullptr && D > K;
-  if (fast) {
+  if (pl.f16) {
     for (int l = 0; l < L; ++l) {
       const bool first = l == 0, lastl = l == L - 1;
       m16 += 12 + (N - 1) * 18.0 + (lastl ? 0 : 18);
@@ -2368,39 +2374,14 @@ extern "C" int pita_egnn_div_work(const pita_egnn_t* net, double* mfma16_per_wal
       m32 += K * (N - 1);
     }
   }
-  if (cached) {  // pita_egnn_jacobian_trace: one launch with the primal, the other D - K directions from the cache
+  if (pl.first) {  // pita_egnn_jacobian_trace: one launch with the primal, the other D - K directions from the cache
     *mfma16_per_walker = (m16 + (D - K) * t16) * tiles_per_walker;
     *mfma32_per_walker = (m32 + (D - K) * t32) * tiles_per_walker;
     return PITA_OK;
   }
+  const double launches = (D + K - 1) / K;
   *mfma16_per_walker = m16 * tiles_per_walker * launches;
   *mfma32_per_walker = m32 * tiles_per_walker * launches;
-  return PITA_OK;
-}
-
-// marks [B] + the flag word behind them (DivParams::bad_flag)
-static int ensure_marks(pita_egnn_t* net, size_t B, hipStream_t st) {
-  if (sizeof(int) * B > net->mark_bytes) {
-    PITA_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(net->d_mark);
-    net->d_mark = nullptr;
-    net->mark_bytes = 0;
-    PITA_HIP_CHECK(hipMalloc(&net->d_mark, sizeof(int) * B + 64));
-    net->mark_bytes = sizeof(int) * B;
-    PITA_HIP_CHECK(hipMemsetAsync(net->d_mark + B, 0, 64, st));
-  }
-  return PITA_OK;
-}
-
-static int div_launch(const DivShape* s, void (*kernel)(DivParams), pita_egnn_t* net, const DivParams& p, void* stream) {
-  const size_t lds = s->lds_bytes(p.n_layers);
-  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
-  const long long ngroups = (p.B + s->G - 1) / s->G;
-  long long want = (ngroups + s->waves - 1) / s->waves;
-  const long long cap = (long long)net->n_cu * s->occ;  // one 4-wave block per CU (one wave per SIMD) unless built for more
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->waves * 64), lds, (hipStream_t)stream, p);
-  PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
 
@@ -2411,49 +2392,46 @@ extern "C" int pita_egnn_div_accumulate(pita_egnn_t* net, const float* h, const 
   PitaDeviceGuard guard(net->device);
   PITA_REQUIRE(h && x && diag_acc, "pita_egnn_div_accumulate: null argument");
   PITA_REQUIRE(beta || net->cfg.in_node_nf == 1, "pita_egnn_div_accumulate: beta required for in_node_nf=2");
-  const int D = net->cfg.n_particles * net->cfg.n_dim;
-  const DivShape* s = find_div_shape(net->cfg.n_particles, net->cfg.n_dim);
-  if (!s) return fail(PITA_EUNSUPPORTED, "pita_egnn_div_accumulate: no kernel for this particle system");
-  const bool fast = div_fast_enabled(net);
-  const DivShape* sf = fast ? find_div_fast_shape(net->cfg.n_particles, net->cfg.n_dim) : s;
-  PITA_REQUIRE(dir0 >= 0 && ndir >= 1 && ndir <= sf->K && dir0 + ndir <= D, "pita_egnn_div_accumulate: directions out of range");
-  DivParams p{};
-  p.mats16 = net->d_mats16; p.mats16h = net->d_mats16h; p.vecs = net->d_vecs; p.vecs_h = net->d_vecs_h;
-  p.vecs_div = net->d_vecs_div;
-  p.n_layers = net->cfg.n_layers; p.in_nf = net->cfg.in_node_nf;
-  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.feature_layout = net->cfg.feature_layout;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
+  const DivPlan pl = div_plan(net);
+  if (!pl.sys) return fail(PITA_EUNSUPPORTED, "pita_egnn_div_accumulate: no kernel for this particle system");
+  const DivSystem& s = *pl.sys;
+  PITA_REQUIRE(dir0 >= 0 && ndir >= 1 && ndir <= s.K && dir0 + ndir <= s.n * s.dim,
+               "pita_egnn_div_accumulate: directions out of range");
+  hipStream_t st = (hipStream_t)stream;
+  DivParams p = div_params(net);
   p.B = B; p.h = h; p.x = x; p.beta = beta; p.dir0 = dir0; p.ndir = ndir; p.diag_acc = diag_acc; p.out = out;
-  if (!fast) return div_launch(s, s->kernel, net, p, stream);
+  const long long grid = div_grid(net, s, B).grid;
+  if (!pl.f16) return div_launch(s.bf16x3, grid, p, st);
   // f16 kernel first: it adds the finite terms and marks the walkers whose term was not; then the bf16x3 kernel
-  // recomputes exactly the marked ones (in chunks of its own K directions)
-  {
-    const int rc0 = ensure_marks(net, (size_t)B, (hipStream_t)stream);
-    if (rc0 != PITA_OK) return rc0;
-  }
+  // recomputes exactly the marked ones
+  const int rc = ensure_marks(net, (size_t)B, st);
+  if (rc != PITA_OK) return rc;
   p.mark = net->d_mark;
   p.bad_flag = net->d_mark + net->mark_bytes / sizeof(int);
   p.bad_seq = ++net->div_seq;
-  int rc = div_launch(sf, sf->fast, net, p, stream);
-  if (rc != PITA_OK) return rc;
+  const int rc1 = div_launch(s.f16, grid, p, st);
+  if (rc1 != PITA_OK) return rc1;
   p.repair = 1;
-  for (int d0 = 0; d0 < ndir; d0 += s->K) {
-    p.dir0 = dir0 + d0;
-    p.ndir = (ndir - d0) < s->K ? (ndir - d0) : s->K;
-    p.out = (d0 == 0) ? out : nullptr;
-    rc = div_launch(s, s->kernel, net, p, stream);
+  return div_launch(s.bf16x3, grid, p, st);
+}
+
+// a full trace (trace zeroed) without the primal cache: pita_egnn_div_accumulate, K directions at a time
+static int div_trace_uncached(pita_egnn_t* net, int K, const float* h, const float* x, const float* beta, float* trace,
+                              float* denoiser_out, int64_t B, void* stream) {
+  const int D = net->cfg.n_particles * net->cfg.n_dim;
+  for (int d0 = 0; d0 < D; d0 += K) {
+    const int rc = pita_egnn_div_accumulate(net, h, x, beta, d0, (D - d0) < K ? (D - d0) : K, trace,
+                                            d0 == 0 ? denoiser_out : nullptr, B, stream);
     if (rc != PITA_OK) return rc;
   }
   return PITA_OK;
 }
 
-
 // Exact trace of the denoiser Jacobian over ALL directions: trace[b] = sum_d (J_x D(h, x) e_d)_d (overwritten), optionally
-// the denoiser itself.  Precision-2 handles with a tangent-only kernel take the primal-cache path: ONE launch of the fast
-// kernel (its own directions, writes the per-edge primal factors), then tangent-only launches
-// that stream the cache -- each followed by the bf16x3 repair pass for marked walkers.  The cache (≈180 KB per walker for
-// LJ13) is owned by the handle; batches whose cache would exceed PITA_DIV_CACHE_GB (default 24) are processed in chunks
-// of walkers.  Other handles loop pita_egnn_div_accumulate.
+// the denoiser itself.  On the primal-cache path (div_plan) ONE launch with the primal writes the per-edge primal
+// factors, then tangent-only launches stream the cache -- each followed by the bf16x3 repair pass for marked walkers.
+// The cache (≈180 KB per walker for LJ13) is owned by the handle; batches whose cache would exceed PITA_DIV_CACHE_GB
+// (default 24) are processed in chunks of walkers.
 extern "C" int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const float* x, const float* beta, float* trace,
                                         float* denoiser_out, int64_t B, void* stream) {
   PITA_REQUIRE(net && B >= 0, "pita_egnn_jacobian_trace: bad argument");
@@ -2461,21 +2439,13 @@ extern "C" int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const 
   PitaDeviceGuard guard(net->device);
   PITA_REQUIRE(h && x && trace, "pita_egnn_jacobian_trace: null argument");
   PITA_REQUIRE(beta || net->cfg.in_node_nf == 1, "pita_egnn_jacobian_trace: beta required for in_node_nf=2");
-  const int n = net->cfg.n_particles, dim = net->cfg.n_dim, D = n * dim, L = net->cfg.n_layers;
-  const DivShape* s = find_div_shape(n, dim);
-  if (!s) return fail(PITA_EUNSUPPORTED, "pita_egnn_jacobian_trace: no kernel for this particle system");
+  const DivPlan pl = div_plan(net);
+  if (!pl.sys) return fail(PITA_EUNSUPPORTED, "pita_egnn_jacobian_trace: no kernel for this particle system");
+  const DivSystem& s = *pl.sys;
+  const int D = s.n * s.dim, L = net->cfg.n_layers;
   hipStream_t st = (hipStream_t)stream;
   PITA_HIP_CHECK(hipMemsetAsync(trace, 0, sizeof(float) * (size_t)B, st));
-  const DivTanShape* ts = div_fast_enabled(net) ? find_div_tan_shape(n, dim, L) : nullptr;
-  if (!ts || ts->G != s->G || (!ts->shared && ts->waves != s->waves) || D <= s->K) {
-    const int K = pita_egnn_div_directions(net);
-    for (int d0 = 0; d0 < D; d0 += K) {
-      const int rc = pita_egnn_div_accumulate(net, h, x, beta, d0, (D - d0) < K ? (D - d0) : K, trace,
-                                              d0 == 0 ? denoiser_out : nullptr, B, stream);
-      if (rc != PITA_OK) return rc;
-    }
-    return PITA_OK;
-  }
+  if (!pl.tangent) return div_trace_uncached(net, s.K, h, x, beta, trace, denoiser_out, B, stream);
   // walkers per chunk: the cache of a chunk must fit the budget
   // budget of the primal cache: PITA_DIV_CACHE_GB, else 24 GB but never more than 60 % of what the device has free
   // right now plus what this handle already holds (other handles, the caller's tensors and a second process keep theirs)
@@ -2491,78 +2461,44 @@ extern "C" int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const 
       (void)hipGetLastError();
     }
   }
-  const double per_walker = 4.0 * (double)ts->group_f(L) / s->G;
+  const double per_walker = 4.0 * (double)s.group_f(L) / s.G;
   long long chunk = (long long)(budget_gb * 1e9 / per_walker);
   chunk = chunk / 1024 * 1024;
   if (chunk < 1024) chunk = 1024;
   if (chunk > B) chunk = B;
-  // cache bytes a chunk of Bc walkers needs (grid of the fast kernel: the cache is indexed by wave and group)
-  // the launch that writes the cache: the system's fast kernel, or a one-direction writer for the block-shared stream
-  const DivShape* wr = ts->shared ? find_div_writer(n, dim) : nullptr;
-  if (wr && (wr->G != s->G || wr->waves != s->waves)) wr = nullptr;
-  const long long grid_cap = (long long)net->n_cu * (wr ? wr->occ : s->occ);
+  // cache bytes a chunk of Bc walkers needs (the cache is indexed by wave and group)
   auto cache_need = [&](long long Bc) -> size_t {
-    const long long ngroups = (Bc + s->G - 1) / s->G;
-    const long long want = (ngroups + s->waves - 1) / s->waves;
-    const long long grid = want < grid_cap ? want : grid_cap;
-    const long long total_waves = grid * s->waves;
-    const long long quota = (Bc + total_waves - 1) / total_waves;
-    return sizeof(float) * ts->group_f(L) * (size_t)(total_waves * ((quota + s->G - 1) / s->G));
+    const DivGrid g = div_grid(net, s, Bc);
+    return sizeof(float) * s.group_f(L) * (size_t)(g.waves * g.groups_per_wave);
   };
   // the buffer is allocated for the largest (= first) chunk; when the device cannot give that much, smaller chunks are
   // tried, and a handle that cannot even cache 1024 walkers falls back to the cache-free launches
-  while (cache_need(chunk) > net->divcache_bytes) {
-    PITA_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(net->d_divcache);
-    net->d_divcache = nullptr;
-    net->divcache_bytes = 0;
-    const size_t need = cache_need(chunk);
-    if (hipMalloc(&net->d_divcache, need) == hipSuccess) {
-      net->divcache_bytes = need;
-      break;
-    }
+  while (grow_scratch(net->d_divcache, net->divcache_bytes, cache_need(chunk), st) != hipSuccess) {
     (void)hipGetLastError();  // out of memory: not sticky
-    net->d_divcache = nullptr;
-    if (chunk <= 1024) {
-      const int K = pita_egnn_div_directions(net);
-      for (int d0 = 0; d0 < D; d0 += K) {
-        const int rc = pita_egnn_div_accumulate(net, h, x, beta, d0, (D - d0) < K ? (D - d0) : K, trace,
-                                                d0 == 0 ? denoiser_out : nullptr, B, stream);
-        if (rc != PITA_OK) return rc;
-      }
-      return PITA_OK;
-    }
+    if (chunk <= 1024) return div_trace_uncached(net, s.K, h, x, beta, trace, denoiser_out, B, stream);
     chunk = (chunk / 2 + 1023) / 1024 * 1024;
   }
+  const DivKernel& tk = *pl.tangent;
+  // full launches first, the remainder last (LJ13: 16, 16, 7).  Round 4 dealt the directions out in equal shares (13, 13,
+  // 13); on the round-5 kernel full launches are 2 % faster per trace for LJ13 (18.35 vs 18.73 ms, four runs each on one
+  // box) and the same for 22 and 55 particles (profiles/r05_tangent_issue_priority.txt)
+  const bool shared = pl.tangent == &s.shared;
+  const int per_launch = shared ? tk.K * tk.waves : tk.K;
   for (long long b0 = 0; b0 < B; b0 += chunk) {
     const long long Bc = (B - b0) < chunk ? (B - b0) : chunk;
-    DivParams p{};
-    p.mats16 = net->d_mats16; p.mats16h = net->d_mats16h; p.vecs = net->d_vecs; p.vecs_h = net->d_vecs_h;
-    p.vecs_div = net->d_vecs_div;
-    p.n_layers = L; p.in_nf = net->cfg.in_node_nf;
-    p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.feature_layout = net->cfg.feature_layout;
-    p.coord_scale = net->cfg.coords_range / (float)L;
+    const DivGrid g = div_grid(net, s, Bc);
+    PITA_REQUIRE(cache_need(Bc) <= net->divcache_bytes, "pita_egnn_jacobian_trace: cache smaller than a chunk");
+    PITA_REQUIRE(g.waves * g.groups_per_wave < 0x7fffffffLL && Bc < 0x7fffffffLL,
+                 "pita_egnn_jacobian_trace: too many walkers in one chunk");
+    const int rc0 = ensure_marks(net, (size_t)Bc, st);
+    if (rc0 != PITA_OK) return rc0;
+    DivParams p = div_params(net);
     p.B = Bc; p.h = h + b0; p.x = x + b0 * D; p.beta = beta ? beta + b0 : nullptr; p.diag_acc = trace + b0;
     p.no_mean = 1;  // all D directions are summed: the mean-free projection's shares cancel (DivParams::no_mean)
-    // grid of the fast / tangent kernels (identical: the cache is indexed by wave and group)
-    const long long ngroups = (Bc + s->G - 1) / s->G;
-    long long want = (ngroups + s->waves - 1) / s->waves;
-    const long long grid = want < grid_cap ? want : grid_cap;
-    const long long total_waves = grid * s->waves;
-    const long long quota = (Bc + total_waves - 1) / total_waves;
-    const long long groups_per_wave = (quota + s->G - 1) / s->G;
-    PITA_REQUIRE(sizeof(float) * ts->group_f(L) * (size_t)(total_waves * groups_per_wave) <= net->divcache_bytes,
-                 "pita_egnn_jacobian_trace: cache smaller than a chunk");
-    {
-      const int rc0 = ensure_marks(net, (size_t)Bc, st);
-      if (rc0 != PITA_OK) return rc0;
-    }
     p.mark = net->d_mark;
     p.bad_flag = net->d_mark + net->mark_bytes / sizeof(int);
     p.cache = net->d_divcache;
-    p.cache_waves = total_waves;
-    PITA_REQUIRE(total_waves * groups_per_wave < 0x7fffffffLL && Bc < 0x7fffffffLL,
-                 "pita_egnn_jacobian_trace: too many walkers in one chunk");
+    p.cache_waves = g.waves;
     auto repair = [&](int dir0, int ndir, float* out) -> int {  // bf16x3 kernel for the marked walkers, its own K at a time
       DivParams r = p;
       r.repair = 1;
@@ -2570,38 +2506,31 @@ extern "C" int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const 
       if (ndir == 0) {  // a launch without directions: only the denoiser of the marked walkers is recomputed
         if (!out) return PITA_OK;
         r.dir0 = 0; r.ndir = 0; r.out = out;
-        return div_launch(s, s->kernel, net, r, stream);
+        return div_launch(s.bf16x3, g.grid, r, st);
       }
       r.dir0 = dir0;
       r.ndir = ndir;
-      r.nchunk = (ndir + s->K - 1) / s->K;
+      r.nchunk = (ndir + s.K - 1) / s.K;
       r.out = out;
-      return div_launch(s, s->kernel, net, r, stream);
+      return div_launch(s.bf16x3, g.grid, r, st);
     };
     // first launch: primal + its own directions, cache written
-    const int first_k = wr ? wr->K : s->K;
-    p.dir0 = 0; p.ndir = first_k < D ? first_k : D; p.out = denoiser_out ? denoiser_out + b0 * D : nullptr;
+    p.dir0 = 0; p.ndir = pl.first->K < D ? pl.first->K : D; p.out = denoiser_out ? denoiser_out + b0 * D : nullptr;
     p.bad_seq = ++net->div_seq;
-    int rc = div_launch(wr ? wr : s, wr ? wr->fast : s->fast, net, p, stream);
+    int rc = div_launch(*pl.first, g.grid, p, st);
     if (rc != PITA_OK) return rc;
     rc = repair(0, p.ndir, p.out);
     if (rc != PITA_OK) return rc;
-    // remaining directions from the cache
+    // remaining directions from the cache; the block-shared kernel puts all its waves on one group
     p.out = nullptr;
-    const size_t lds = ts->lds_bytes(L);
-    PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ts->kernel), lds));
-    // full launches first, the remainder last (LJ13: 16, 16, 7).  Round 4 dealt the directions out in equal shares (13, 13,
-    // 13); on the round-5 kernel full launches are 2 % faster per trace for LJ13 (18.35 vs 18.73 ms, four runs each on one
-    // box) and the same for 22 and 55 particles (profiles/r05_tangent_issue_priority.txt)
-    const int per_launch = ts->shared ? ts->K * ts->waves : ts->K;
-    const long long tgrid = !ts->shared ? grid : (total_waves * groups_per_wave < (long long)net->n_cu
-                                                      ? total_waves * groups_per_wave : (long long)net->n_cu);
-    for (int d0 = first_k; d0 < D; d0 += per_launch) {
+    const long long groups = g.waves * g.groups_per_wave;
+    const long long tgrid = !shared ? g.grid : (groups < (long long)net->n_cu ? groups : (long long)net->n_cu);
+    for (int d0 = pl.first->K; d0 < D; d0 += per_launch) {
       p.dir0 = d0;
       p.ndir = (D - d0) < per_launch ? (D - d0) : per_launch;
       p.bad_seq = ++net->div_seq;
-      hipLaunchKernelGGL(ts->kernel, dim3((unsigned)tgrid), dim3(ts->waves * 64), lds, st, p);
-      PITA_LAUNCH_CHECK();
+      rc = div_launch(tk, tgrid, p, st);
+      if (rc != PITA_OK) return rc;
       rc = repair(d0, p.ndir, nullptr);
       if (rc != PITA_OK) return rc;
     }

@@ -359,13 +359,11 @@ static size_t jvp_lds_bytes_of(int L) { return JvpCfg<N, DIM, G, WAVES>::lds_byt
   JvpShape { N, DIM, G, WAVES, OCC, egnn_jvp_kernel<N, DIM, G, WAVES, OCC>, jvp_lds_bytes_of<N, DIM, G, WAVES> }
 static const JvpShape kJvpShapes[] = {
     PITA_JVP_SHAPE(4, 2, 8, 4, 1),
-    PITA_JVP_SHAPE(13, 3, 7, 4, 1),
+    // LJ13: one column tile per wave (2 walkers, 26 of 32 columns) at two waves per SIMD measured 8 % faster than
+    // three dense tiles (7 walkers) at one wave per SIMD (3.28 vs 3.57 ms per launch at 65 536 walkers)
+    PITA_JVP_SHAPE(13, 3, 2, 4, 2),
     PITA_JVP_SHAPE(22, 3, 4, 4, 1),
     PITA_JVP_SHAPE(55, 3, 1, 4, 1),
-    // LJ13: one column tile per wave (2 walkers, 26 of 32 columns) at two waves per SIMD measured 8 % faster than
-    // three dense tiles at one wave per SIMD (3.28 vs 3.57 ms per launch at 65 536 walkers); PITA_JVP_ALT=0 selects
-    // the dense shape above
-    PITA_JVP_SHAPE(13, 3, 2, 4, 2),
 };
 
 }  // namespace pita
@@ -383,9 +381,8 @@ extern "C" int pita_egnn_jvp(pita_egnn_t* net, const float* h, const float* x, c
   const int D = net->cfg.n_particles * net->cfg.n_dim;
   PITA_REQUIRE(vx || (dir >= -1 && dir < D), "pita_egnn_jvp: dir out of range");
   const JvpShape* s = nullptr;
-  static const int alt = getenv("PITA_JVP_ALT") ? atoi(getenv("PITA_JVP_ALT")) : 1;
   for (const auto& c : kJvpShapes)
-    if (c.n == net->cfg.n_particles && c.dim == net->cfg.n_dim && (c.occ == 1 || alt)) s = &c;
+    if (c.n == net->cfg.n_particles && c.dim == net->cfg.n_dim) s = &c;
   if (!s) return fail(PITA_EUNSUPPORTED, "pita_egnn_jvp: no kernel for this particle system");
   JvpParams p{};
   p.mats16 = net->d_mats16; p.vecs = net->d_vecs; p.n_layers = net->cfg.n_layers; p.in_nf = net->cfg.in_node_nf;

@@ -868,9 +868,25 @@ static const EgnnShape* shape_for(const pita_egnn_t* net, long long B) {
   return waves_s < two_per_simd ? t : s;
 }
 
+// the mapping of B walkers: shape, LDS, blocks wanted (one group per wave) and resident blocks (LDS and the 256-VGPR
+// budget: 2 waves per SIMD = two 4-wave blocks per CU); the sampler runs a persistent grid-stride grid of grid() blocks
+struct EgnnMapping {
+  const EgnnShape* s;
+  size_t lds;
+  long long want, cap;
+  long long grid() const { return want < cap ? want : cap; }
+};
+static EgnnMapping egnn_mapping(const pita_egnn_t* net, long long B) {
+  const EgnnShape* s = shape_for(net, B);
+  const size_t lds = s->lds_bytes(net->cfg.n_layers);
+  int blocks_per_cu = (int)((160 * 1024) / lds);
+  blocks_per_cu = blocks_per_cu < 1 ? 1 : (blocks_per_cu > s->occ ? s->occ : blocks_per_cu);
+  const long long ngroups = (B + s->G - 1) / s->G;
+  return {s, lds, (ngroups + s->waves - 1) / s->waves, (long long)net->n_cu * blocks_per_cu};
+}
+
 static int egnn_launch(pita_egnn_t* net, EgnnParams& p, void* stream) {
   PitaDeviceGuard guard(net->device);
-  const EgnnShape* s = shape_for(net, p.B);
   const int prec = net->cfg.precision;
   p.mats = net->d_mats;
   p.mats16 = net->d_mats16;
@@ -883,27 +899,15 @@ static int egnn_launch(pita_egnn_t* net, EgnnParams& p, void* stream) {
   p.feature_layout = net->cfg.feature_layout;
   p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
   if (p.B == 0) return PITA_OK;
-  const long long ngroups = (p.B + s->G - 1) / s->G;
-  const size_t lds = s->lds_bytes(p.n_layers);
-  // resident blocks per CU: limited by LDS and by the 256-VGPR budget (2 waves per SIMD = two 4-wave blocks)
-  int blocks_per_cu = (int)((160 * 1024) / lds);
-  blocks_per_cu = blocks_per_cu < 1 ? 1 : (blocks_per_cu > s->occ ? s->occ : blocks_per_cu);
-  long long want = (ngroups + s->waves - 1) / s->waves;
-  long long cap = (long long)net->n_cu * blocks_per_cu;
-  // forward modes: one group per wave (plain grid); sampler mode: persistent grid-stride
-  unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (p.mode != 3) grid = (unsigned)want;
+  const EgnnMapping m = egnn_mapping(net, p.B);
+  const EgnnShape* s = m.s;
+  const size_t lds = m.lds;
   const int smp = p.mode == 3 ? 1 : 0;
+  const unsigned grid = (unsigned)(smp ? m.grid() : m.want);  // forward modes: one group per wave
   if (prec == 2 && smp) {  // keep the walkers: the repair launch restarts the affected groups from them
-    const size_t need = sizeof(float) * (size_t)p.B * s->n * s->dim + sizeof(int) * (size_t)p.B * s->n;
-    if (need > net->bk_bytes) {
-      PITA_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));  // an earlier launch may still use the old buffer
-      (void)hipFree(net->d_bk);
-      net->d_bk = nullptr;
-      net->bk_bytes = 0;
-      PITA_HIP_CHECK(hipMalloc(&net->d_bk, need));
-      net->bk_bytes = need;
-    }
+    PITA_HIP_CHECK(grow_scratch(net->d_bk, net->bk_bytes,
+                                sizeof(float) * (size_t)p.B * s->n * s->dim + sizeof(int) * (size_t)p.B * s->n,
+                                (hipStream_t)stream));
     float* xb = static_cast<float*>(net->d_bk);
     PITA_HIP_CHECK(hipMemcpyAsync(xb, p.x, sizeof(float) * (size_t)p.B * s->n * s->dim, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream));
@@ -929,14 +933,9 @@ static int egnn_launch(pita_egnn_t* net, EgnnParams& p, void* stream) {
 extern "C" int pita_egnn_sampler_work(const pita_egnn_t* net, int64_t B, double* mfma16_per_walker_step,
                                       double* mfma32_per_walker_step) {
   PITA_REQUIRE(net && B > 0 && mfma16_per_walker_step && mfma32_per_walker_step, "pita_egnn_sampler_work: bad argument");
-  const EgnnShape* s = shape_for(net, B);
-  const int L = net->cfg.n_layers, N = s->n, G = s->G;
-  const size_t lds = s->lds_bytes(L);
-  int blocks_per_cu = (int)((160 * 1024) / lds);
-  blocks_per_cu = blocks_per_cu < 1 ? 1 : (blocks_per_cu > s->occ ? s->occ : blocks_per_cu);
-  const long long ngroups = (B + G - 1) / G;
-  long long want = (ngroups + s->waves - 1) / s->waves, cap = (long long)net->n_cu * blocks_per_cu;
-  const long long total_waves = (want < cap ? want : cap) * s->waves;
+  const EgnnMapping m = egnn_mapping(net, B);
+  const int L = net->cfg.n_layers, N = m.s->n, G = m.s->G;
+  const long long total_waves = m.grid() * m.s->waves;
   const long long quota = (B + total_waves - 1) / total_waves;
   double tiles = 0.0;  // live column tiles per step, summed over all waves
   for (long long wbeg = 0; wbeg < B; wbeg += quota) {
@@ -963,15 +962,10 @@ extern "C" int pita_egnn_sampler_work(const pita_egnn_t* net, int64_t B, double*
 extern "C" int pita_egnn_sampler_mapping(const pita_egnn_t* net, int64_t B, int* walkers_per_group, int64_t* waves,
                                          int64_t* wave_slots) {
   PITA_REQUIRE(net && B > 0 && walkers_per_group && waves && wave_slots, "pita_egnn_sampler_mapping: bad argument");
-  const EgnnShape* s = shape_for(net, B);  // the same arithmetic as egnn_launch (mode 3)
-  const size_t lds = s->lds_bytes(net->cfg.n_layers);
-  int blocks_per_cu = (int)((160 * 1024) / lds);
-  blocks_per_cu = blocks_per_cu < 1 ? 1 : (blocks_per_cu > s->occ ? s->occ : blocks_per_cu);
-  const long long ngroups = (B + s->G - 1) / s->G;
-  const long long want = (ngroups + s->waves - 1) / s->waves, cap = (long long)net->n_cu * blocks_per_cu;
-  *walkers_per_group = s->G;
-  *waves = (want < cap ? want : cap) * s->waves;
-  *wave_slots = cap * s->waves;
+  const EgnnMapping m = egnn_mapping(net, B);
+  *walkers_per_group = m.s->G;
+  *waves = m.grid() * m.s->waves;
+  *wave_slots = m.cap * m.s->waves;
   return PITA_OK;
 }
 

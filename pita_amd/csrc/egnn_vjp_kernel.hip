@@ -660,10 +660,15 @@ static const VjpShape kVjpShapes[] = {
 static const VjpShape kVjpShapesSmall[] = {
     PITA_VJP_SHAPE(13, 3, 2, 4),
 };
-// column-tile passes of the busiest wave: (groups per wave) x (tiles per group)
-static long long vjp_passes(const VjpShape& s, long long B, long long wave_slots) {
+// the launch over B walkers: at most one block per CU (one wave per SIMD); passes: column-tile passes of the busiest
+// wave, (groups per wave) x (tiles per group)
+struct VjpGrid {
+  long long grid, passes;
+};
+static VjpGrid vjp_grid(const VjpShape& s, long long B, long long n_cu) {
   const long long ngroups = (B + s.G - 1) / s.G;
-  return ((ngroups + wave_slots - 1) / wave_slots) * ((s.G * s.n + 31) / 32);
+  const long long want = (ngroups + s.waves - 1) / s.waves, slots = n_cu * s.waves;
+  return {want < n_cu ? want : n_cu, ((ngroups + slots - 1) / slots) * ((s.G * s.n + 31) / 32)};
 }
 
 }  // namespace pita
@@ -683,9 +688,7 @@ extern "C" int pita_egnn_vjp(pita_egnn_t* net, const float* h, const float* x, c
     if (c.n == net->cfg.n_particles && c.dim == net->cfg.n_dim) s = &c;
   if (!s) return fail(PITA_EUNSUPPORTED, "pita_egnn_vjp: no kernel for this particle system");
   for (const auto& c : kVjpShapesSmall)  // fewer tile passes on the busiest wave with the small groups: take them
-    if (c.n == s->n && c.dim == s->dim &&
-        vjp_passes(c, B, (long long)net->n_cu * c.waves) < vjp_passes(*s, B, (long long)net->n_cu * s->waves))
-      s = &c;
+    if (c.n == s->n && c.dim == s->dim && vjp_grid(c, B, net->n_cu).passes < vjp_grid(*s, B, net->n_cu).passes) s = &c;
   VjpParams p{};
   p.mats16 = net->d_mats16; p.vecs = net->d_vecs; p.n_layers = net->cfg.n_layers; p.in_nf = net->cfg.in_node_nf;
   p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.feature_layout = net->cfg.feature_layout;
@@ -694,26 +697,16 @@ extern "C" int pita_egnn_vjp(pita_egnn_t* net, const float* h, const float* x, c
   p.dot_parts = dot_parts;
   const size_t lds = s->lds_bytes(p.n_layers);
   const int fixed = (p.attention && p.tanh_on && dot_h) ? 1 : 0;
-  static const bool force_bf16 = getenv("PITA_VJP_BF16") != nullptr;  // development aid: A/B against the bf16x3 edge GEMMs
-  const bool f16 = net->cfg.precision == 2 && !force_bf16;
+  const bool f16 = net->cfg.precision == 2;
   p.mats16h = net->d_mats16h;
   hipStream_t st = (hipStream_t)stream;
   auto configure = [&](const void* k) -> int {
     PITA_HIP_CHECK(ensure_dynamic_lds(k, lds));
     return PITA_OK;
   };
-  const long long ngroups = (B + s->G - 1) / s->G;
-  long long want = (ngroups + s->waves - 1) / s->waves;
-  const long long cap = net->n_cu;  // one 4-wave block per CU (one wave per SIMD)
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  const size_t need = sizeof(float) * s->ws_f(p.n_layers) * (size_t)grid * s->waves;
-  if (net->ws_bytes < need) {  // checkpoint scratch, owned by the handle (one stream at a time, see pita_hip.h)
-    PITA_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(net->d_ws);
-    net->d_ws = nullptr; net->ws_bytes = 0;
-    PITA_HIP_CHECK(hipMalloc(&net->d_ws, need));
-    net->ws_bytes = need;
-  }
+  const unsigned grid = (unsigned)vjp_grid(*s, B, net->n_cu).grid;
+  // checkpoint scratch, owned by the handle (one stream at a time, see pita_hip.h)
+  PITA_HIP_CHECK(grow_scratch(net->d_ws, net->ws_bytes, sizeof(float) * s->ws_f(p.n_layers) * (size_t)grid * s->waves, st));
   p.ws = net->d_ws;
   const auto kernel = s->kernel[fixed];
   if (!f16) {
@@ -725,13 +718,7 @@ extern "C" int pita_egnn_vjp(pita_egnn_t* net, const float* h, const float* x, c
   }
   // f16 edge GEMMs first; walkers that came out non-finite are marked and recomputed by the bf16x3 kernel, which returns
   // at once when nothing was marked
-  if (sizeof(int) * ((size_t)B + 16) > net->vjp_mark_bytes) {
-    PITA_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(net->d_vjp_mark);
-    net->d_vjp_mark = nullptr; net->vjp_mark_bytes = 0;
-    PITA_HIP_CHECK(hipMalloc(&net->d_vjp_mark, sizeof(int) * ((size_t)B + 16)));
-    net->vjp_mark_bytes = sizeof(int) * ((size_t)B + 16);
-  }
+  PITA_HIP_CHECK(grow_scratch(net->d_vjp_mark, net->vjp_mark_bytes, sizeof(int) * ((size_t)B + 16), st));
   int* mark = net->d_vjp_mark;
   int* flag = mark + B;
   PITA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));

@@ -1024,11 +1024,48 @@ extern "C" int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net) {
 
 extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
   if (!net) return PITA_OK;
+  PitaDeviceGuard guard(net->device);
   wide64_release(net);
   (void)hipFree(net->d_vjp_ws);
   (void)hipFree(net->d_w);
   (void)hipFree(net->d_estatic);
   delete net;
+  return PITA_OK;
+}
+
+static WideParams wide_params(const pita_egnn_wide_t* net, long long B, int mode) {
+  WideParams p{};
+  p.w = net->d_w; p.estatic = net->d_estatic;
+  p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
+  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
+  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
+  p.B = B; p.mode = mode;
+  return p;
+}
+
+// A vector-pipe launch over B walkers, one walker per wave: per_wave bytes of LDS each, four waves per block halved until
+// a block needs at most block_cap bytes, at most blocks_per_cu blocks per CU
+struct WideGrid {
+  int waves;
+  size_t lds;
+  unsigned grid;
+};
+static int wide_grid(const char* fn, const pita_egnn_wide_t* net, size_t per_wave, size_t block_cap, long long blocks_per_cu,
+                     long long B, WideGrid& g) {
+  int waves = 4;
+  while (waves > 1 && per_wave * waves > block_cap) waves >>= 1;
+  if (per_wave * waves > 150 * 1024)
+    return fail(PITA_EUNSUPPORTED, "%s: %d particles need %zu B of LDS per wave", fn, net->cfg.n_particles, per_wave);
+  const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu * blocks_per_cu;
+  g = {waves, per_wave * waves, (unsigned)(want < cap ? want : cap)};
+  return PITA_OK;
+}
+template <class P>
+static int wide_launch(const char* fn, void (*kernel)(P), const WideGrid& g, const P& q, hipStream_t st) {
+  if (ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), g.lds) != hipSuccess)
+    return fail(PITA_EHIP, "%s: cannot reserve %zu B of LDS", fn, g.lds);
+  hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(g.waves * 64), g.lds, st, q);
+  if (hipGetLastError() != hipSuccess) return fail(PITA_EHIP, "%s: launch failed", fn);
   return PITA_OK;
 }
 
@@ -1039,41 +1076,23 @@ extern "C" int pita_egnn_wide_eval(pita_egnn_wide_t* net, int what, const float*
   if (B == 0) return PITA_OK;
   PITA_REQUIRE(t && x && out, "pita_egnn_wide_eval: null argument");
   PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_eval: beta required (condition_beta)");
-  int prev = -1;
-  bool switched = false;
-  if (net->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != net->device)
-    switched = hipSetDevice(net->device) == hipSuccess;
-  WideParams p{};
-  p.w = net->d_w; p.estatic = net->d_estatic;
-  p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
-  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.B = B; p.mode = what; p.x = x; p.t = t; p.beta = beta; p.out = out;
-  int rc = PITA_OK;
+  PitaDeviceGuard guard(net->device);
+  WideParams p = wide_params(net, B, what);
+  p.x = x; p.t = t; p.beta = beta; p.out = out;
   // matrix-pipe kernel first where the particle system has one; the vector-pipe kernel then recomputes the walkers whose
   // result came out non-finite (an activation beyond the f16 range) and returns at once for all others
   if (pita_egnn_wide_uses_matrix_pipe(net)) {
-    rc = wide64_launch(net, what, t, x, beta, out, B, (hipStream_t)stream);
+    const int rc = wide64_launch(net, what, t, x, beta, out, B, (hipStream_t)stream);
+    if (rc != PITA_OK) return rc;
     p.only_bad = 1;
     p.bad_flag = net->d_flag;
   }
-  const size_t per_wave = sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 3 * p.n * 4 + WIDE_HP);
-  int waves = 4;
-  while (waves > 1 && per_wave * waves > 72 * 1024) waves >>= 1;  // two blocks per CU inside the 160 KB
-  auto kernel = p.H <= 32 ? egnn_wide_kernel<32, false> : egnn_wide_kernel<64, false>;
-  if (rc != PITA_OK) {
-  } else if (per_wave * waves > 150 * 1024) {
-    rc = fail(PITA_EUNSUPPORTED, "pita_egnn_wide_eval: %d particles need %zu B of LDS per wave", p.n, per_wave);
-  } else if (ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), per_wave * waves) != hipSuccess) {
-    rc = fail(PITA_EHIP, "pita_egnn_wide_eval: cannot reserve %zu B of LDS", per_wave * waves);
-  } else {
-    const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu * 8;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), per_wave * waves, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_eval: launch failed");
-  }
-  if (switched) (void)hipSetDevice(prev);
-  return rc;
+  WideGrid g;  // two blocks per CU inside the 160 KB
+  const int rc = wide_grid("pita_egnn_wide_eval", net, sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 3 * p.n * 4 + WIDE_HP),
+                           72 * 1024, 8, B, g);
+  if (rc != PITA_OK) return rc;
+  return wide_launch("pita_egnn_wide_eval", p.H <= 32 ? egnn_wide_kernel<32, false> : egnn_wide_kernel<64, false>, g, p,
+                     (hipStream_t)stream);
 }
 
 // Forward-mode derivative of the denoiser around the wide backbone (vector-pipe kernel; see egnn_wide_jvp_kernel)
@@ -1086,60 +1105,30 @@ extern "C" int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const f
   PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_jvp: beta required (condition_beta)");
   PITA_REQUIRE(dir < net->cfg.n_particles * net->cfg.n_dim, "pita_egnn_wide_jvp: direction %d out of range", dir);
   PITA_REQUIRE(!diag_acc || (dir >= 0 && !vx), "pita_egnn_wide_jvp: diag_acc needs a unit direction");
-  int prev = -1;
-  bool switched = false;
-  if (net->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != net->device)
-    switched = hipSetDevice(net->device) == hipSuccess;
+  PitaDeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
   WideJvpParams q{};
   WideParams& p = q.base;
-  p.w = net->d_w; p.estatic = net->d_estatic;
-  p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
-  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.B = B; p.mode = 1; p.x = x; p.t = h; p.beta = beta; p.out = out;
+  p = wide_params(net, B, 1);
+  p.x = x; p.t = h; p.beta = beta; p.out = out;
   q.vx = vx; q.vh = vh; q.dir = vx ? -1 : dir; q.dout = dout; q.dot_out = dot_out; q.dot_stride = dot_stride;
   q.dot_off = dot_off; q.diag_acc = diag_acc;
-  int rc = PITA_OK;
   // matrix-pipe kernel first where the particle system has one (PITA_WIDE_NO_MFMA: the vector-pipe kernel alone); it
   // flags the walkers whose primal or tangent left the f16 range and the vector-pipe kernel below computes exactly those
   if (pita_egnn_wide_uses_matrix_pipe(net)) {
     const size_t need = sizeof(int) * (size_t)B;
-    if (need > net->jbad_bytes) {
-      hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-      (void)hipFree(net->d_jbad);
-      net->d_jbad = nullptr;
-      net->jbad_bytes = 0;
-      if (e == hipSuccess) e = hipMalloc(&net->d_jbad, need);
-      if (e != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_jvp: flag buffer: %s", hipGetErrorString(e));
-      else net->jbad_bytes = need;
-    }
-    if (rc == PITA_OK && hipMemsetAsync(net->d_jbad, 0, need, (hipStream_t)stream) != hipSuccess)
-      rc = fail(PITA_EHIP, "pita_egnn_wide_jvp: memset failed");
-    if (rc == PITA_OK) {
-      const int r64 = wide64_jvp(net, h, x, beta, vx, dir, vh, out, dout, dot_out, dot_stride, dot_off, diag_acc, net->d_jbad,
-                                 B, (hipStream_t)stream);
-      if (r64 == PITA_OK) q.only_bad = net->d_jbad;
-      else if (r64 != 1) rc = r64;
-    }
+    PITA_HIP_CHECK(grow_scratch(net->d_jbad, net->jbad_bytes, need, st));
+    PITA_HIP_CHECK(hipMemsetAsync(net->d_jbad, 0, need, st));
+    const int r64 = wide64_jvp(net, h, x, beta, vx, dir, vh, out, dout, dot_out, dot_stride, dot_off, diag_acc, net->d_jbad,
+                               B, st);
+    if (r64 == PITA_OK) q.only_bad = net->d_jbad;
+    else if (r64 != 1) return r64;
   }
-  const size_t per_wave = sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + 2 * WIDE_HP);
-  int waves = 4;
-  while (waves > 1 && per_wave * waves > 150 * 1024) waves >>= 1;
-  auto kernel = p.H <= 32 ? egnn_wide_jvp_kernel<32> : egnn_wide_jvp_kernel<64>;
-  
-  if (rc != PITA_OK) {
-  } else if (per_wave * waves > 150 * 1024) {
-    rc = fail(PITA_EUNSUPPORTED, "pita_egnn_wide_jvp: %d particles need %zu B of LDS per wave", p.n, per_wave);
-  } else if (ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), per_wave * waves) != hipSuccess) {
-    rc = fail(PITA_EHIP, "pita_egnn_wide_jvp: cannot reserve %zu B of LDS", per_wave * waves);
-  } else {
-    const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu * 2;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), per_wave * waves, (hipStream_t)stream, q);
-    if (hipGetLastError() != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_jvp: launch failed");
-  }
-  if (switched) (void)hipSetDevice(prev);
-  return rc;
+  WideGrid g;
+  const int rc = wide_grid("pita_egnn_wide_jvp", net, sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + 2 * WIDE_HP),
+                           150 * 1024, 2, B, g);
+  if (rc != PITA_OK) return rc;
+  return wide_launch("pita_egnn_wide_jvp", p.H <= 32 ? egnn_wide_jvp_kernel<32> : egnn_wide_jvp_kernel<64>, g, q, st);
 }
 
 // Fused sampler on the wide backbone: n_steps Euler-Maruyama steps of the NOT-debiased reverse VE-SDE in one launch
@@ -1153,62 +1142,31 @@ extern "C" int pita_egnn_wide_sampler_run(pita_egnn_wide_t* net, float* x, int64
   PITA_REQUIRE(net && B >= 0 && n_steps >= 0, "pita_egnn_wide_sampler_run: bad argument");
   if (B == 0 || n_steps == 0) return PITA_OK;
   PITA_REQUIRE(x && step_tab, "pita_egnn_wide_sampler_run: null argument");
-  int prev = -1;
-  bool switched = false;
-  if (net->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != net->device)
-    switched = hipSetDevice(net->device) == hipSuccess;
+  PitaDeviceGuard guard(net->device);
   hipStream_t st = (hipStream_t)stream;
-  WideParams p{};
-  p.w = net->d_w; p.estatic = net->d_estatic;
-  p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
-  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.B = B; p.mode = 3; p.xs = x; p.step_tab = step_tab; p.n_steps = n_steps; p.noise = noise; p.seed = seed;
+  WideParams p = wide_params(net, B, 3);
+  p.xs = x; p.step_tab = step_tab; p.n_steps = n_steps; p.noise = noise; p.seed = seed;
   p.walker_offset = walker_offset; p.step0 = step0; p.remove_mean = remove_mean; p.stats_out = stats_out;
-  int rc = PITA_OK;
-  const size_t nx = (size_t)B * p.n * p.dim;
   if (pita_egnn_wide_uses_matrix_pipe(net)) {
-    const size_t need = sizeof(float) * nx + sizeof(int) * (size_t)B * p.n;
-    if (need > net->bk_bytes) {
-      hipError_t e = hipStreamSynchronize(st);  // an earlier launch may still use the old buffer
-      (void)hipFree(net->d_bk);
-      net->d_bk = nullptr;
-      net->bk_bytes = 0;
-      if (e == hipSuccess) e = hipMalloc(&net->d_bk, need);
-      if (e != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_sampler_run: backup buffer: %s", hipGetErrorString(e));
-      else net->bk_bytes = need;
-    }
-    if (rc == PITA_OK) {
-      float* xb = static_cast<float*>(net->d_bk);
-      int* bad_from = reinterpret_cast<int*>(xb + nx);
-      if (hipMemcpyAsync(xb, x, sizeof(float) * nx, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        rc = fail(PITA_EHIP, "pita_egnn_wide_sampler_run: backup copy failed");
-      if (rc == PITA_OK)
-        rc = wide64_sampler(net, x, B, step_tab, n_steps, noise, seed, walker_offset, step0, remove_mean, stats_out,
-                            bad_from, st);
-      p.only_bad = 1;
-      p.x_backup = xb;
-      p.bad_from = bad_from;
-      p.bad_flag = net->d_flag;
-    }
+    const size_t nx = (size_t)B * p.n * p.dim;
+    PITA_HIP_CHECK(grow_scratch(net->d_bk, net->bk_bytes, sizeof(float) * nx + sizeof(int) * (size_t)B * p.n, st));
+    float* xb = static_cast<float*>(net->d_bk);
+    int* bad_from = reinterpret_cast<int*>(xb + nx);
+    PITA_HIP_CHECK(hipMemcpyAsync(xb, x, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
+    const int rc = wide64_sampler(net, x, B, step_tab, n_steps, noise, seed, walker_offset, step0, remove_mean, stats_out,
+                                  bad_from, st);
+    if (rc != PITA_OK) return rc;
+    p.only_bad = 1;
+    p.x_backup = xb;
+    p.bad_from = bad_from;
+    p.bad_flag = net->d_flag;
   }
-  const size_t per_wave = sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 4 * p.n * 4 + WIDE_HP);
-  int waves = 4;
-  while (waves > 1 && per_wave * waves > 72 * 1024) waves >>= 1;
-  auto kernel = p.H <= 32 ? egnn_wide_kernel<32, true> : egnn_wide_kernel<64, true>;
-  if (rc != PITA_OK) {
-  } else if (per_wave * waves > 150 * 1024) {
-    rc = fail(PITA_EUNSUPPORTED, "pita_egnn_wide_sampler_run: %d particles need %zu B of LDS per wave", p.n, per_wave);
-  } else if (ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), per_wave * waves) != hipSuccess) {
-    rc = fail(PITA_EHIP, "pita_egnn_wide_sampler_run: cannot reserve %zu B of LDS", per_wave * waves);
-  } else {
-    const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu * 8;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), per_wave * waves, st, p);
-    if (hipGetLastError() != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_sampler_run: launch failed");
-  }
-  if (switched) (void)hipSetDevice(prev);
-  return rc;
+  WideGrid g;
+  const int rc = wide_grid("pita_egnn_wide_sampler_run", net,
+                           sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 4 * p.n * 4 + WIDE_HP), 72 * 1024, 8, B, g);
+  if (rc != PITA_OK) return rc;
+  return wide_launch("pita_egnn_wide_sampler_run", p.H <= 32 ? egnn_wide_kernel<32, true> : egnn_wide_kernel<64, true>, g,
+                     p, st);
 }
 
 // Reverse-mode derivative of the denoiser around the wide backbone (see egnn_wide_vjp_kernel); arguments as pita_egnn_vjp
@@ -1218,44 +1176,20 @@ extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const f
   if (B == 0) return PITA_OK;
   PITA_REQUIRE(h && x && vjp, "pita_egnn_wide_vjp: null argument");
   PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_vjp: beta required (condition_beta)");
-  int prev = -1;
-  bool switched = false;
-  if (net->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != net->device)
-    switched = hipSetDevice(net->device) == hipSuccess;
+  PitaDeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
   WideVjpParams q{};
   WideParams& p = q.base;
-  p.w = net->d_w; p.estatic = net->d_estatic;
-  p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
-  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.B = B; p.mode = 1; p.x = x; p.t = h; p.beta = beta; p.out = out;
+  p = wide_params(net, B, 1);
+  p.x = x; p.t = h; p.beta = beta; p.out = out;
   q.cot = cot; q.vjp = vjp; q.dot_h = dot_h;
-  int rc = PITA_OK;
-  const size_t per_wave = sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + WIDE_HP);
-  int waves = 4;
-  while (waves > 1 && per_wave * waves > 150 * 1024) waves >>= 1;
-  auto kernel = p.H <= 32 ? egnn_wide_vjp_kernel<32> : egnn_wide_vjp_kernel<64>;
-  const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu;  // one wave per SIMD
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  const size_t ws_need = sizeof(float) * (size_t)grid * waves * p.L * ((size_t)2 * p.n * WIDE_HP + (size_t)p.n * 4);
-  if (per_wave * waves > 150 * 1024) {
-    rc = fail(PITA_EUNSUPPORTED, "pita_egnn_wide_vjp: %d particles need %zu B of LDS per wave", p.n, per_wave);
-  } else if (ws_need > net->vjp_ws_bytes) {
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);  // an earlier launch may still use the old buffer
-    (void)hipFree(net->d_vjp_ws);
-    net->d_vjp_ws = nullptr;
-    net->vjp_ws_bytes = 0;
-    if (e == hipSuccess) e = hipMalloc(&net->d_vjp_ws, ws_need);
-    if (e != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_vjp: checkpoint buffer: %s", hipGetErrorString(e));
-    else net->vjp_ws_bytes = ws_need;
-  }
-  if (rc == PITA_OK && ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), per_wave * waves) != hipSuccess)
-    rc = fail(PITA_EHIP, "pita_egnn_wide_vjp: cannot reserve %zu B of LDS", per_wave * waves);
-  if (rc == PITA_OK) {
-    q.ws = net->d_vjp_ws;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), per_wave * waves, (hipStream_t)stream, q);
-    if (hipGetLastError() != hipSuccess) rc = fail(PITA_EHIP, "pita_egnn_wide_vjp: launch failed");
-  }
-  if (switched) (void)hipSetDevice(prev);
-  return rc;
+  WideGrid g;  // one wave per SIMD
+  const int rc = wide_grid("pita_egnn_wide_vjp", net, sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + WIDE_HP),
+                           150 * 1024, 1, B, g);
+  if (rc != PITA_OK) return rc;
+  // per-wave checkpoints of the forward sweep
+  PITA_HIP_CHECK(grow_scratch(net->d_vjp_ws, net->vjp_ws_bytes,
+                              sizeof(float) * (size_t)g.grid * g.waves * p.L * ((size_t)2 * p.n * WIDE_HP + (size_t)p.n * 4), st));
+  q.ws = net->d_vjp_ws;
+  return wide_launch("pita_egnn_wide_vjp", p.H <= 32 ? egnn_wide_vjp_kernel<32> : egnn_wide_vjp_kernel<64>, g, q, st);
 }

@@ -1839,6 +1839,22 @@ def test_jacobian_trace_network_variants(pa, golden, variant):
     np.testing.assert_allclose(tr.cpu().numpy(), acc.cpu().numpy(), rtol=2e-5, atol=2e-5 * scale)
 
 
+@pytest.mark.parametrize("n,d,want16,want32", [(13, 3, 2889, 252), (55, 3, 132012, 18144), (4, 2, 105.75, 4.125),
+                                                  (22, 3, 13338, 1449)])
+def test_div_work_of_default_handles(pa, n, d, want16, want32):
+    """pita_egnn_div_work prices the debiased leg's roofline (bench.py): for the default h32 x 3 handles (f16x2, primal-cache
+    path) it counts the matrix instructions per walker of one full trace.  The counts depend on the plan
+    pita_egnn_jacobian_trace takes, not on the batch or the device."""
+    import ctypes
+
+    net = pa.EGNN_dynamics(n, d, hidden_nf=32, n_layers=3, recurrent=True, tanh=True, attention=True, condition_time=True,
+                           condition_temperature=True, agg="sum", precision="f16x2")
+    a, b = ctypes.c_double(), ctypes.c_double()
+    pa._lib.check(pa._lib.lib().pita_egnn_div_work(net._native(torch.device("cuda", 0)), ctypes.byref(a), ctypes.byref(b)),
+                  "pita_egnn_div_work")
+    assert (a.value, b.value) == (want16, want32)
+
+
 def test_jacobian_trace_22_atoms_four_layers(pa, golden):
     """22 atoms x 4 layers: the sweep's piece sequence exceeds the block-shared kernel's table, so the wave-owned
     tangent kernel must take over (a silent overflow would give garbage)."""
