@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PITA_ABI_VERSION 11
+#define PITA_ABI_VERSION 12
 
 enum {
   PITA_OK = 0,
@@ -417,6 +417,29 @@ int pita_mlp_sampler_run(pita_mlp_t* net, float* x, int64_t B, const float* step
                          const float* noise /*nullable*/, uint64_t seed, uint64_t walker_offset, int64_t step0,
                          int remove_mean, int n_particles, int n_dim, double* stats_out /*nullable, as above*/,
                          void* stream);
+/* Derivatives of the MLP's EDM denoiser D(h, x) = c_s x + c_out F(c_noise, c_in x, beta), c_noise = ln(h)/8 (score_net.py:
+ * 13-43 around mlp.py:11-24, 100-118, 244-267, 501-524), for the debiased Feynman-Kac regime (sdes.py:151-239).  They
+ * replace the reference's vmap(jacrev) (utils.py:30-51), autograd of E_theta (energy_net.py:51-62) and its
+ * h-derivative (sdes.py:218).  Forward mode: the primal tile and up to K tangent tiles share one weight stream (K = 4, 2,
+ * 1 for hidden 32, 64, 128; more directions run in passes).  h and x are the unscaled per-walker noise level and
+ * coordinates; c_in, c_noise, c_s, c_out are computed in-kernel.  beta (device [B]) is read for
+ * MyMLPTemperature only and not differentiated.  Requires out_dim == input_dim <= 64, else PITA_EUNSUPPORTED.
+ * Every output is nullable and work that no requested output needs is skipped:
+ *   out_D[b]      = D(h_b, x_b)                                          [B, D]
+ *   trace[b]      = tr(J_x D)                                            [B]  (overwritten)
+ *   vjp[b]        = J_x D^T cot, (J^T cot)_k = <cot, J e_k> from the same unit tangents   [B, D]
+ *   dot_h[b]      = <cot, dD/dh>                                         [B]
+ *   dot_parts[b]  = (c_out <cot, F>, <cot, d(c_out F)/dh>) as pita_egnn_vjp defines it    [B, 2]
+ * cot: device [B, D] or NULL (= x). */
+int pita_mlp_jacobian(pita_mlp_t* net, const float* h, const float* x, const float* beta /*nullable*/,
+                      const float* cot /*nullable*/, float* out_D, float* trace, float* vjp, float* dot_h,
+                      float* dot_parts, int64_t B, void* stream);
+/* One forward-mode tangent of the same denoiser; parameter list and semantics of pita_egnn_jvp:
+ * dout = J_x D . vx + dD/dh . vh (vx NULL: unit direction dir, -1 = none; vh NULL = 0), out = D,
+ * dot_out[b*dot_stride + dot_off] = <x_b, dD_b>, diag_acc[b] += dD[b, dir]. */
+int pita_mlp_jvp(pita_mlp_t* net, const float* h, const float* x, const float* beta, const float* vx, int dir,
+                 const float* vh, float* out /*nullable*/, float* dout /*nullable*/, float* dot_out /*nullable*/,
+                 int64_t dot_stride, int64_t dot_off, float* diag_acc /*nullable*/, int64_t B, void* stream);
 
 /* ---------------------------------------------------------------- elementwise sampler pieces
  * K8: x <- x + drift*dt + (noise_scale*xi)*sqrt_dt, then optional per-walker mean removal

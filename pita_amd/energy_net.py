@@ -2,9 +2,11 @@
 
 * ``forward_energy`` -- E_theta(h, x) (energy_net.py:14-49): one backbone forward on the EDM-scaled input
   (``pita_edm_scale_input``), then the per-walker reduction kernel ``pita_energy_theta``.
-* ``forward`` -- grad_x E_theta (autograd in the reference, :51-62): ONE reverse-mode launch of the HIP EGNN
-  (``EGNN_dynamics.vjp``): grad E = ((1 + c_s) x - D - J_x D^T x) / h; backbones with a forward-mode derivative only
-  (``EGNN_dynamics_AD2_cat.jvp``) assemble J_x D^T x from one launch per direction.
+* ``forward`` -- grad_x E_theta (autograd in the reference, :51-62): grad E = ((1 + c_s) x - D - J_x D^T x) / h with
+  J_x D^T x from the backbone's ``vjp`` -- ONE reverse-mode launch of the HIP EGNN (``EGNN_dynamics.vjp``), ONE
+  forward-mode launch over all D unit tangents of the HIP MLP (``MyMLP.vjp`` / ``MyMLPTemperature.vjp``,
+  pita_mlp_jacobian); backbones with a single-direction forward-mode derivative only (``EGNN_dynamics_AD2_cat.jvp``)
+  assemble it from one launch per direction.
 """
 import torch
 from torch import nn
@@ -48,7 +50,8 @@ class EnergyNet(nn.Module):
 
     def forward(self, ht, xt, beta, pin=False, t=None, energy_function=None):
         if pin or self.precondition_beta or not (hasattr(self.net, "vjp") or hasattr(self.net, "jvp")):
-            raise NotImplementedError("EnergyNet.forward: needs a HIP EGNN backbone, pin=False, precondition_beta=False")
+            raise NotImplementedError("EnergyNet.forward: needs a HIP backbone with a derivative (EGNN_dynamics, "
+                                      "EGNN_dynamics_AD2_cat, MyMLP, MyMLPTemperature), pin=False, precondition_beta=False")
         x = _lib.dev_tensor(xt, "xt")
         h = self._batch(ht, x.shape[0], x.device)
         if hasattr(self.net, "vjp"):

@@ -4,7 +4,8 @@ Mirror of ``MyMLP`` (pita/src/models/components/mlp.py:199-267) and ``MyMLPTempe
 (:453-524): sinusoidal embedding of every input coordinate (scale 25), of time (and of beta),
 Linear -> GELU, ``hidden_layers`` residual GELU blocks, Linear.  Same constructor arguments,
 parameter names (``joint_mlp.N[.ff].{weight,bias}``) and creation order as the reference, so
-seeded construction and checkpoints carry over.  The arithmetic is pita_amd/csrc/mlp_kernel.hip.
+seeded construction and checkpoints carry over.  The arithmetic is pita_amd/csrc/mlp_kernel.hip; the derivatives of
+the EDM denoiser that the debiased regime needs (``jvp``, ``vjp``, ``jacobian_trace``) are csrc/mlp_jac_kernel.hip.
 """
 import ctypes
 
@@ -91,6 +92,80 @@ class _HipMLP(nn.Module):
                                                out.data_ptr(), B, _lib.stream_ptr(x.device)), "pita_mlp_forward")
         return out
 
+    # ------------------------------------------------------------------ derivatives of the EDM denoiser (debiased regime)
+    # Same contracts as EGNN_dynamics.jvp / vjp / jacobian_trace; one launch each (csrc/mlp_jac_kernel.hip).
+    def _prep(self, h_t, x_t, beta):
+        x_t = _lib.dev_tensor(x_t, "x_t")
+        B = x_t.shape[0]
+        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
+        b = _as_batch(beta, B, x_t.device) if self._temperature else None
+        return h_t, x_t, b
+
+    def jvp(self, h_t, x_t, beta, vx=None, direction=-1, vh=None, want_primal=True, want_tangent=True, dot_out=None,
+            dot_col=0, diag_acc=None):
+        """(D, dD): the denoiser D_theta(h, x) and its forward-mode derivative along ONE tangent direction:
+        dD = J_x D . vx + dD/dh . vh.  ``vx``: [B, D] tensor, or None for the unit direction ``direction`` of
+        every walker (-1 = zero).  ``vh``: [B] tensor or None.  Optional in-kernel reductions:
+        ``dot_out[:, dot_col] = <x, dD>`` and ``diag_acc += dD[:, direction]`` (pita_mlp_jvp)."""
+        h_t, x_t, b = self._prep(h_t, x_t, beta)
+        B = x_t.shape[0]
+        if vx is not None:
+            vx = _lib.dev_tensor(vx, "vx")
+        if vh is not None:
+            vh = _lib.dev_tensor(vh, "vh").reshape(-1).expand(B).contiguous()
+        out = torch.empty_like(x_t) if want_primal else None
+        dout = torch.empty_like(x_t) if want_tangent else None
+        stride = 1
+        if dot_out is not None:
+            assert dot_out.is_cuda and dot_out.dtype == torch.float32 and dot_out.is_contiguous()
+            stride = dot_out.shape[1] if dot_out.dim() == 2 else 1
+        _lib.check(_lib.lib().pita_mlp_jvp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
+                                           _lib.ptr(vx), int(direction), _lib.ptr(vh), _lib.ptr(out), _lib.ptr(dout),
+                                           _lib.ptr(dot_out), stride, int(dot_col), _lib.ptr(diag_acc), B,
+                                           _lib.stream_ptr(x_t.device)), "pita_mlp_jvp")
+        return out, dout
+
+    def jacobian(self, h_t, x_t, beta, cot=None, want_denoiser=False, want_trace=False, want_vjp=False,
+                 want_dot_h=False, want_h_parts=False):
+        """Every requested derivative of D_theta(h, x) from ONE launch of pita_mlp_jacobian, as a dict with the keys
+        ``D`` [B, D], ``trace`` [B], ``vjp`` = J_x D^T cot [B, D], ``dot_h`` = <cot, dD/dh> [B] and ``h_parts`` [B, 2]
+        (``cot`` default: x)."""
+        h_t, x_t, b = self._prep(h_t, x_t, beta)
+        B = x_t.shape[0]
+        if cot is not None:
+            cot = _lib.dev_tensor(cot, "cot")
+        dev = x_t.device
+        res = {"D": torch.empty_like(x_t) if want_denoiser else None,
+               "trace": torch.empty(B, device=dev) if want_trace else None,
+               "vjp": torch.empty_like(x_t) if want_vjp else None,
+               "dot_h": torch.empty(B, device=dev) if want_dot_h else None,
+               "h_parts": torch.empty(B, 2, device=dev) if want_h_parts else None}
+        _lib.check(_lib.lib().pita_mlp_jacobian(self._native(dev), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
+                                                _lib.ptr(cot), _lib.ptr(res["D"]), _lib.ptr(res["trace"]),
+                                                _lib.ptr(res["vjp"]), _lib.ptr(res["dot_h"]), _lib.ptr(res["h_parts"]),
+                                                B, _lib.stream_ptr(dev)), "pita_mlp_jacobian")
+        return res
+
+    def jacobian_trace(self, h_t, x_t, beta, want_denoiser=False):
+        """trace(J_x D_theta(h, x)) per walker, exactly, over all D unit directions (one launch; the tangents share
+        the primal's weight stream).  ``want_denoiser``: also return D_theta(h, x) -> (trace, D)."""
+        r = self.jacobian(h_t, x_t, beta, want_denoiser=want_denoiser, want_trace=True)
+        return (r["trace"], r["D"]) if want_denoiser else r["trace"]
+
+    vjp_h_parts = True  # vjp(..., want_h_parts=True) is available
+
+    def vjp(self, h_t, x_t, beta, cot=None, want_primal=True, want_dot_h=False, want_h_parts=False):
+        """(D, J_x D^T cot) for a per-walker cotangent (default: x_t), assembled in-kernel from the D unit tangents:
+        (J^T cot)_k = <cot, J e_k>.  ``want_dot_h``: also <cot, dD/dh> [B] -> (D, vjp, dot_h).  ``want_h_parts`` (with
+        want_dot_h): also [B, 2] = (c_out <cot, F>, <cot, d(c_out F)/dh>) -> (D, vjp, dot_h, parts); the contract
+        of EGNN_dynamics.vjp."""
+        if want_h_parts and not want_dot_h:
+            raise ValueError("want_h_parts needs want_dot_h")
+        r = self.jacobian(h_t, x_t, beta, cot=cot, want_denoiser=want_primal, want_vjp=True, want_dot_h=want_dot_h,
+                          want_h_parts=want_h_parts)
+        if want_h_parts:
+            return r["D"], r["vjp"], r["dot_h"], r["h_parts"]
+        return (r["D"], r["vjp"], r["dot_h"]) if want_dot_h else (r["D"], r["vjp"])
 
     def sampler_run(self, x, step_tab, n_steps, noise=None, seed=0, walker_offset=0, step0=0, remove_mean=True,
                     drift_out=None, n_particles=None, n_dim=None, stats_out=None):
@@ -126,3 +201,9 @@ class MyMLPTemperature(_HipMLP):
 
     def forward(self, t, x, beta):
         return self._run(t, x, beta)
+
+
+def _as_batch(v, B, device):
+    if isinstance(v, torch.Tensor):
+        return _lib.dev_tensor(v.to(device), "beta").reshape(-1).expand(B).contiguous()
+    return torch.full((B,), float(v), device=device, dtype=torch.float32)

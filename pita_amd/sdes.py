@@ -8,11 +8,14 @@
 * Debiased Feynman-Kac regime (sdes.py:151-239): drift_X = -gamma grad_x E_theta g^2/2 + gamma s_theta g^2/2 and the
   log-weight drift  gamma^2 <-grad E, b> + gamma div b + gamma dE/dt + gamma'(t) E, clamped at its 0.9 quantile.
   The reference obtains grad_x E (autograd), div s (vmap(jacrev)) and dE/dt (autograd through h(t)); here they are
-  assembled (pita_fk_assemble, csrc/fk_kernels.hip) from derivatives of the two denoisers computed by HIP kernels:
-  ONE reverse-mode launch on the energy net (pita_egnn_vjp, csrc/egnn_vjp_kernel.hip) that returns J_x D^T x and
-  <x, dD/dh> from the same sweep, and the exact trace of the score net's Jacobian (pita_egnn_jacobian_trace,
-  csrc/egnn_div_kernel.hip: one launch with the primal that writes the primal cache, tangent-only launches that stream
-  it), per step; the clamp is pita_quantile_clamp per inference chunk.
+  assembled (pita_fk_assemble, csrc/fk_kernels.hip) from derivatives of the two denoisers computed by HIP kernels.
+  EGNN backbones: ONE reverse-mode launch on the energy net (pita_egnn_vjp, csrc/egnn_vjp_kernel.hip) that returns
+  J_x D^T x and <x, dD/dh> from the same sweep, and the exact trace of the score net's Jacobian
+  (pita_egnn_jacobian_trace, csrc/egnn_div_kernel.hip: one launch with the primal that writes the primal cache,
+  tangent-only launches that stream it).  MLP backbones (MyMLP / MyMLPTemperature): one forward-mode launch per net
+  (pita_mlp_jacobian, csrc/mlp_jac_kernel.hip) whose D unit tangents and h tangent share the primal's weight stream
+  and give J_x D^T x, <x, dD/dh> and the trace in-kernel.  Per step; the clamp is pita_quantile_clamp per inference
+  chunk.  Any backbone with ``jvp`` (and optionally ``vjp`` / ``jacobian_trace``) runs this regime.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -153,7 +156,7 @@ class VEReverseSDE:
         The per-walker reductions happen inside the kernel; only [B] / [B, D] results touch memory."""
         if not hasattr(model, "jvp"):
             raise NotImplementedError(
-                "debias_inference=True needs a backbone with a forward-mode derivative (the HIP EGNN_dynamics.jvp)")
+                "debias_inference=True needs a backbone with a forward-mode derivative (jvp: the HIP EGNN and MLP backbones)")
         B, D = x.shape
         trace = torch.zeros(B, device=x.device)
         jtx = torch.empty(B, D, device=x.device)
