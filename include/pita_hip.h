@@ -412,7 +412,12 @@ int pita_mlp_forward(pita_mlp_t* net, const float* t, const float* x, const floa
                      float* out, int64_t B, void* stream);
 /* Fused not-debiased sampler for the MLP backbone: the counterpart of pita_egnn_sampler_run (same step table, noise and
  * Philox conventions; sde_integration.py:299-351 + sdes.py:117-128 + score_net.py:13-43) with the walkers LDS-resident
- * for all n_steps.  Requires out_dim == input_dim == n_particles * n_dim <= 64 (GMM: n_particles = 1, n_dim = 2). */
+ * for all n_steps.  Requires out_dim == input_dim == n_particles * n_dim, 1 <= input_dim <= 64 and n_dim <= 4 (GMM:
+ * n_particles = 1, n_dim = 2); anything else is refused with an error code before a launch.  The walkers take
+ * 1 024 * input_dim bytes of dynamic LDS (64 KB at input_dim = 64) next to 12 KB of static LDS for the weight stream;
+ * the launcher does not raise the kernel's dynamic-LDS limit.  Observed with ROCm 7.2.0 on gfx950: the whole range
+ * launches and computes correctly (tests/test_mlp_shapes_gpu.py runs input_dim = 52, 53 and 64).  B = 0 or n_steps = 0
+ * returns without a launch (as do pita_mlp_forward, pita_mlp_jacobian and pita_mlp_jvp at B = 0). */
 int pita_mlp_sampler_run(pita_mlp_t* net, float* x, int64_t B, const float* step_tab, int n_steps,
                          const float* noise /*nullable*/, uint64_t seed, uint64_t walker_offset, int64_t step0,
                          int remove_mean, int n_particles, int n_dim, double* stats_out /*nullable, as above*/,

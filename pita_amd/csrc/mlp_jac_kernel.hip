@@ -313,8 +313,10 @@ using namespace pita;
 
 static int mlp_jac_check(const pita_mlp* net, const float* h, const float* x, const float* beta, int64_t B,
                          const char* who) {
-  PITA_REQUIRE(net && h && x && B >= 0, "%s: null argument", who);
-  PITA_REQUIRE(beta || !net->cfg.temperature_conditioned, "%s: beta required (temperature_conditioned)", who);
+  PITA_REQUIRE(net && B >= 0, "%s: bad argument", who);
+  // an empty batch has null data pointers: the callers return before any launch
+  PITA_REQUIRE(B == 0 || (h && x), "%s: null argument", who);
+  PITA_REQUIRE(B == 0 || beta || !net->cfg.temperature_conditioned, "%s: beta required (temperature_conditioned)", who);
   const int D = net->cfg.input_dim;
   if (net->cfg.out_dim != D)
     return fail(PITA_EUNSUPPORTED, "%s: the denoiser's Jacobian needs out_dim == input_dim (got %d, %d)", who,

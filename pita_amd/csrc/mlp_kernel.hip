@@ -370,9 +370,10 @@ extern "C" int pita_mlp_destroy(pita_mlp_t* net) {
 
 extern "C" int pita_mlp_forward(pita_mlp_t* net, const float* t, const float* x, const float* beta, float* out,
                                 int64_t B, void* stream) {
-  PITA_REQUIRE(net && t && x && out && B >= 0, "pita_mlp_forward: null argument");
+  PITA_REQUIRE(net && B >= 0, "pita_mlp_forward: bad argument");
+  if (B == 0) return PITA_OK;  // an empty batch has null data pointers
+  PITA_REQUIRE(t && x && out, "pita_mlp_forward: null argument");
   PITA_REQUIRE(beta || !net->cfg.temperature_conditioned, "pita_mlp_forward: beta required (temperature_conditioned)");
-  if (B == 0) return PITA_OK;
   MlpParams p = net->p;
   p.B = B; p.t = t; p.x = x; p.beta = beta; p.out = out;
   const long long nblk = ((B + 31) / 32 + 3) / 4;
@@ -395,8 +396,9 @@ extern "C" int pita_mlp_forward(pita_mlp_t* net, const float* t, const float* x,
 extern "C" int pita_mlp_sampler_run(pita_mlp_t* net, float* x, int64_t B, const float* step_tab, int n_steps,
                                     const float* noise, uint64_t seed, uint64_t walker_offset, int64_t step0,
                                     int remove_mean, int n_particles, int n_dim, double* stats_out, void* stream) {
-  PITA_REQUIRE(net && x && step_tab && B >= 0 && n_steps >= 0, "pita_mlp_sampler_run: bad argument");
-  if (n_steps == 0 || B == 0) return PITA_OK;
+  PITA_REQUIRE(net && B >= 0 && n_steps >= 0, "pita_mlp_sampler_run: bad argument");
+  if (n_steps == 0 || B == 0) return PITA_OK;  // an empty batch has null data pointers
+  PITA_REQUIRE(x && step_tab, "pita_mlp_sampler_run: null argument");
   const int D = net->cfg.input_dim;
   PITA_REQUIRE(net->cfg.out_dim == D, "pita_mlp_sampler_run: the score net must map R^D to R^D");
   PITA_REQUIRE(D <= 64, "pita_mlp_sampler_run: input_dim <= 64");

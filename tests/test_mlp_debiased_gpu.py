@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import pita_oracle as O
+from tests._mlp_shapes import _oracle_derivs  # fp64 D, F, J_x D, dD/dh by vmap(jacrev); shared with test_mlp_shapes_*
 
 pytestmark = pytest.mark.gpu
 T = torch.tensor
@@ -47,19 +48,6 @@ def _net(kind, golden):
         kw = dict(emb_size=32, hidden_layers=2, temperature_conditioned=True)
     wd = {k: v.double() for k, v in net.state_dict().items()}
     return net, wd, kw
-
-
-def _oracle_derivs(bb, h, x, beta):
-    """fp64: D, F, J_x D [B, D, D], dD/dh [B, D] by vmap(jacrev) through O.denoiser."""
-    from torch.func import jacrev, vmap
-
-    def one(h1, x1, b1):
-        return O.denoiser(bb, h1.reshape(1), x1.reshape(1, -1), b1.reshape(1)).squeeze(0)
-
-    dDdh, J = vmap(jacrev(one, argnums=(0, 1)))(h, x, beta)
-    c_s, c_in, c_out, c_noise = O.edm_coeffs(h)
-    F = bb(c_noise, c_in[:, None] * x, beta)
-    return O.denoiser(bb, h, x, beta), F, J, dDdh
 
 
 @pytest.mark.parametrize("kind", ["gmm", "temp", "h32"])
