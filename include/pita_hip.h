@@ -213,8 +213,8 @@ typedef struct {
  * device call.  The handle carries one launch plan for both entry points: floor(256 / n_atoms) walkers per block, or
  * fewer where the device's per-block LDS cannot hold the interaction tables (bonded terms, the dense pair table,
  * per-atom lists) plus that many walkers' working set; where not even one walker fits, PITA_EUNSUPPORTED with the bytes
- * needed and available.  A handle that exists is therefore taken by both pita_ff_logp_force and pita_ff_descent, and a
- * walker's result does not depend on the plan. */
+ * needed and available.  A handle that exists is therefore taken by pita_ff_logp_force, pita_ff_descent and
+ * pita_ff_mala (which lives in the descent's footprint), and a walker's result does not depend on the plan. */
 int pita_ff_create(pita_ff_t** out, const pita_ff_config* cfg);
 int pita_ff_destroy(pita_ff_t* ff);
 int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, float* force /*nullable*/, int64_t B, void* stream);
@@ -226,6 +226,28 @@ int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, float* force 
 int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise /*nullable*/, int64_t B, int n_steps, float dt,
                     float noise_scale, float sqrt_dt, uint64_t seed, uint64_t walker_offset, int64_t step0,
                     int remove_mean, void* stream);
+
+/* Fused MALA chain on the force-field target: metropolis_hastings_mala / _adaptive
+ * (pita/src/models/components/sde_integration.py:28-45,362-470) with the target of alp_energy.py:122-149; bit-identical
+ * to pita_ff_logp_force + pita_mala_propose + pita_ff_logp_force + pita_mala_accept + pita_mala_adapt step after step.
+ * Contract and argument meaning of pita_lj_mala: x [B, 3 n_atoms] and logp [B] (log-density of x on entry) are updated in
+ * place; dt_dev holds the step size (adapted in place when adaptive != 0, against the acceptance rate over `total`
+ * walkers -- this rank's B); rates_out [n_steps] receives the acceptance rates.  noise [n_steps, B, 3 n] / uniforms
+ * [n_steps, B] nullable -> Philox keyed (seed, walker key, step0 + s, atom / 0xFFFFF), walker key = walker_ids[w] or
+ * walker_offset + w.  workspace: 8-byte aligned device scratch of pita_ff_mala_workspace_bytes(n_steps) bytes.
+ * A non-adaptive chain is ONE launch with the walkers resident on chip over all steps.  An adaptive chain is one launch
+ * per step: the order of the stream is what lets a step see the acceptance count of the step before, and every launch
+ * derives its step size on the device from dt_dev[0] and the counts so far (no host synchronisation).  There is no
+ * grid-wide barrier and no wait inside the kernel, so this entry point cannot time out: it has no NaN result and no
+ * rerun protocol, unlike pita_lj_mala / pita_dw_mala.  The chain runs in the launch plan of pita_ff_descent, so a handle
+ * that exists is taken; PITA_EUNSUPPORTED is reserved for a handle whose plan cannot hold the chain.
+ * ff, dt_dev, workspace non-null, B >= 0, n_steps >= 0, total > 0 and the workspace alignment are checked before any
+ * device call (PITA_EINVAL); B == 0 or n_steps == 0 is PITA_OK and leaves dt_dev as it is. */
+size_t pita_ff_mala_workspace_bytes(int n_steps);
+int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* noise /*nullable [n_steps,B,3n]*/,
+                 const float* uniforms /*nullable [n_steps,B]*/, int64_t B, int n_steps, double* dt_dev, int adaptive,
+                 int64_t total, uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids /*nullable*/,
+                 int64_t step0, int remove_mean, float* rates_out /*nullable*/, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------- EGNN backbone (K5, K7)
  * replaces EGNN_dynamics.forward (pita/src/models/components/egnn_temp_conditioned.py:56-93,

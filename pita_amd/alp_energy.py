@@ -103,7 +103,7 @@ class ForceFieldEnergy(BaseMoleculeEnergy):
         tors_idx[nt,4], tors_par[nt,3], charge[n], sigma[n], epsilon[n], exc_idx[ne,2], exc_par[ne,3]; optional
         gb_radius[n], gb_scale[n] switch the GB-OBC1 implicit solvent on (OpenMM GBSAOBCForce parameters).
         Up to 256 atoms (alanine di-, tri- and tetra-peptide and beyond): the kernel handle takes as many walkers per
-        block as the device's LDS holds with these tables, the same for ``__call__`` and ``fused_descent``."""
+        block as the device's LDS holds with these tables, the same for ``__call__``, ``fused_descent`` and ``fused_mala``."""
         assert spatial_dim == 3
         super().__init__(dimensionality=3 * n_particles, n_particles=n_particles, spatial_dim=3, data_path=None,
                          device=device, is_molecule=is_molecule, temperature=temperature, should_normalize=False,
@@ -179,6 +179,26 @@ class ForceFieldEnergy(BaseMoleculeEnergy):
                 self._native(), x.data_ptr(), _lib.ptr(noise), x.shape[0], int(num_steps), float(dt), float(noise_scale),
                 float(sqrt_dt), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step0), int(bool(remove_mean)),
                 _lib.stream_ptr(x.device)), "pita_ff_descent")
+        return x
+
+    def fused_mala(self, x, logp, num_steps, dt_dev, adaptive, total, noise=None, uniforms=None, seed=0, walker_offset=0,
+                   walker_ids=None, step0=0, remove_mean=True, rates_out=None):
+        """All ``num_steps`` MALA steps in place on ``x`` / ``logp`` / ``dt_dev`` (pita_ff_mala;
+        metropolis_hastings_mala(_adaptive), sde_integration.py:362-470), bit-identical to the launch-per-kernel path:
+        one launch for a non-adaptive chain, one per step for an adaptive one, no grid barrier in either.  Returns ``x``
+        when the launch ran, None when the handle's launch plan cannot hold the chain (PITA_EUNSUPPORTED): the caller
+        then runs the launch-per-kernel path.  The whole batch goes in one grid-striding launch (``energy_batch_size``
+        of ALPEnergy only chunks ``__call__``; a walker's result does not depend on its batch)."""
+        L = _lib.lib()
+        ws = torch.empty((int(L.pita_ff_mala_workspace_bytes(int(num_steps))) + 7) // 8, device=x.device, dtype=torch.int64)
+        with torch.cuda.device(x.device):
+            rc = L.pita_ff_mala(self._native(), x.data_ptr(), logp.data_ptr(), _lib.ptr(noise), _lib.ptr(uniforms),
+                                x.shape[0], int(num_steps), dt_dev.data_ptr(), int(bool(adaptive)), int(total),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), _lib.ptr(walker_ids), int(step0),
+                                int(bool(remove_mean)), _lib.ptr(rates_out), ws.data_ptr(), _lib.stream_ptr(x.device))
+        if rc == -2:  # PITA_EUNSUPPORTED
+            return None
+        _lib.check(rc, "pita_ff_mala")
         return x
 
 

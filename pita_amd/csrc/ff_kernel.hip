@@ -12,13 +12,13 @@
 // GPU of BASELINE config C4 put a wave on every SIMD) unless the LDS cannot hold that many (launch plan, pita_ff_create);
 // coordinates and tables live in LDS; loads and stores of x / force are contiguous spans.  ~14 kflop (+ ~60 kflop with
 // GB-OBC1) and 536 B per walker-eval for a 22-atom peptide: compute- rather than bandwidth-bound.
-#include "common.h"
+#include "pair_common.h"  // launch_mala_finish (common.h comes with it)
 
 namespace pita {
 
 struct FfParams {
   int n, nb, na, nt, np;
-  int wpb;               // walkers per block: the launch plan of pita_ff_create, the same for both entry points
+  int wpb;               // walkers per block: the launch plan of pita_ff_create, the same for every entry point
   // tables (inside `blob`): bond_idx[nb][2], bond_par[nb][2], angle_idx[na][3], angle_par[na][2], tors_idx[nt][4],
   // tors_par[nt][3], pair_idx[np][2], pair_par[np][4] = (ONE_4PI_EPS0*qq, sigma, 4*eps, is_exception)
   float length_scale, inv_kT, cutoff, krf, crf;
@@ -49,33 +49,268 @@ struct FfParams {
 // LDS executes ds_add_f32 at well under one lane per clock).  Per-atom interaction lists (CSR) are built on the host.
 constexpr int FF_THREADS = 256;
 
+// A block's dynamic LDS: the interaction tables, then the per-walker arrays of p.wpb walkers
+struct FfLds {
+  const int *bond_idx, *angle_idx, *tors_idx, *csr_off, *csr_ent;
+  const float *bond_par, *angle_par, *tors_par, *tors_cs, *pair_par, *gb_par;
+  float *xs, *gs, *es, *br, *bw, *tg, *xu, *vv;
+  int n_slots;
+};
+
+// Stages the tables (no barrier: the first __syncthreads of the caller, after it has filled xs, covers them) and carves
+// the per-walker arrays.
+__device__ __forceinline__ FfLds ff_stage(const FfParams& p, float* sm) {
+  const int n = p.n, D = 3 * n, WPB = p.wpb;
+  FfLds L;
+  // interaction tables: LDS-resident for the whole (persistent) block
+  unsigned* tb = reinterpret_cast<unsigned*>(sm);
+  for (int i = threadIdx.x; i < p.blob_words; i += FF_THREADS) tb[i] = p.blob[i];
+  L.bond_idx = reinterpret_cast<const int*>(tb + p.o_bond_idx);
+  L.bond_par = reinterpret_cast<const float*>(tb + p.o_bond_par);
+  L.angle_idx = reinterpret_cast<const int*>(tb + p.o_angle_idx);
+  L.angle_par = reinterpret_cast<const float*>(tb + p.o_angle_par);
+  L.tors_idx = reinterpret_cast<const int*>(tb + p.o_tors_idx);
+  L.tors_par = reinterpret_cast<const float*>(tb + p.o_tors_par);
+  L.tors_cs = reinterpret_cast<const float*>(tb + p.o_tors_cs);  // [nt][2] cos, sin of the phase
+  L.pair_par = reinterpret_cast<const float*>(tb + p.o_pair_par);
+  L.gb_par = reinterpret_cast<const float*>(tb + p.o_gb_par);
+  L.csr_off = reinterpret_cast<const int*>(tb + p.o_csr_off);  // [3][n+1]: bonds, angles, torsions
+  L.csr_ent = reinterpret_cast<const int*>(tb + p.o_csr_ent);  // (term << 2) | role
+  L.xs = sm + p.blob_words;     // [WPB][D] coordinates (nm)
+  L.gs = L.xs + WPB * D;        // [WPB][D] gradient, for the coalesced store (MALA: the accept step's reductions)
+  L.es = L.gs + WPB * D;        // [WPB][n] energy partials
+  L.br = L.es + WPB * n;        // [WPB][n] Born radii
+  L.bw = L.br + WPB * n;        // [WPB][n] dE/d(HCT sum)
+  L.n_slots = 2 * p.nb + 3 * p.na + 4 * p.nt;  // gradient slots of the bonded terms: one per (term, participating atom)
+  L.tg = L.bw + WPB * n;        // [WPB][n_slots][3] bonded-term gradients, phase 1 -> phase 2
+  L.xu = L.tg + WPB * 3 * L.n_slots;  // DESCENT, MALA: [WPB][D] walkers in model units, resident over the steps
+  L.vv = L.xu + WPB * D;        // DESCENT: [WPB][D] updated walkers before the centring; MALA: proposals, then the selection
+  return L;
+}
+
+// Energy partial E (kJ/mol; the walker's energy is the sum over its atoms) and gradient g (kJ/mol/nm) of atom a of
+// walker wl at the coordinates in L.xs (nm), which the caller has filled and fenced with __syncthreads.  Every thread
+// of the block calls it (barriers inside); threads without a walker (act false) compute nothing.  The caller needs a
+// __syncthreads before it overwrites xs or calls again.  One function for all entry points: logp / force, descent and
+// MALA evaluate a walker with the same instruction sequence.
+__device__ __forceinline__ void ff_eval(const FfParams& p, const FfLds& L, bool act, int wl, int a, float& E_out,
+                                        float& g0_out, float& g1_out, float& g2_out) {
+  const int n = p.n, D = 3 * n, n_slots = L.n_slots;
+  const int *bond_idx = L.bond_idx, *angle_idx = L.angle_idx, *tors_idx = L.tors_idx, *csr_off = L.csr_off, *csr_ent = L.csr_ent;
+  const float *bond_par = L.bond_par, *angle_par = L.angle_par, *tors_par = L.tors_par, *tors_cs = L.tors_cs;
+  const float *pair_par = L.pair_par, *gb_par = L.gb_par;
+  float *xs = L.xs, *br = L.br, *bw = L.bw, *tg = L.tg;
+  const float* xr = xs + (act ? wl : 0) * D;
+  const float xa0 = xr[3 * a % D], xa1 = xr[(3 * a + 1) % D], xa2 = xr[(3 * a + 2) % D];
+  float E = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f;
+  // ---- bonded terms, two phases (round 6).  Phase 1: one thread per TERM (the walker's threads deal the bonds, angles and
+  //      torsions out among themselves) evaluates it ONCE and parks the gradient of every participating atom in LDS;
+  //      phase 2: one thread per ATOM adds up its slots through the per-atom lists.  Before, every participating atom
+  //      re-evaluated the whole term (angles 3x, torsions 4x, with acosf / atan2f / sinf / cosf each time) and the atom
+  //      sitting in the most torsions set the pace of its wave.
+  {
+    float* tgw = tg + (act ? wl : 0) * (3 * n_slots);
+    if (act) {
+      // HarmonicBondForce: 1/2 k (r - r0)^2; slots [2 t + role]
+      for (int t = a; t < p.nb; t += n) {
+        const int i = 3 * bond_idx[2 * t], j = 3 * bond_idx[2 * t + 1];
+        const float r0 = bond_par[2 * t], k = bond_par[2 * t + 1];
+        const float d0 = xr[i] - xr[j], d1 = xr[i + 1] - xr[j + 1], d2 = xr[i + 2] - xr[j + 2];
+        const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2)));
+        const float dr = r - r0;
+        E = fmaf(0.5f * k * dr, dr, E);
+        const float c = k * dr / r;
+        float* o = tgw + 3 * (2 * t);
+        o[0] = c * d0; o[1] = c * d1; o[2] = c * d2;
+        o[3] = -c * d0; o[4] = -c * d1; o[5] = -c * d2;
+      }
+      // HarmonicAngleForce: 1/2 k (theta - theta0)^2; slots [2 nb + 3 t + role]
+      for (int t = a; t < p.na; t += n) {
+        const int i = 3 * angle_idx[3 * t], j = 3 * angle_idx[3 * t + 1], k3 = 3 * angle_idx[3 * t + 2];
+        const float th0 = angle_par[2 * t], k = angle_par[2 * t + 1];
+        float av[3], bv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { av[c] = xr[i + c] - xr[j + c]; bv[c] = xr[k3 + c] - xr[j + c]; }
+        const float aa = fmaf(av[0], av[0], fmaf(av[1], av[1], av[2] * av[2]));
+        const float bb = fmaf(bv[0], bv[0], fmaf(bv[1], bv[1], bv[2] * bv[2]));
+        const float ab = fmaf(av[0], bv[0], fmaf(av[1], bv[1], av[2] * bv[2]));
+        const float inv = 1.0f / sqrtf(aa * bb);
+        const float cosv = fminf(fmaxf(ab * inv, -1.0f), 1.0f);
+        const float dth = acosf(cosv) - th0;
+        E = fmaf(0.5f * k * dth, dth, E);
+        const float sinv = fmaxf(sqrtf(fmaf(-cosv, cosv, 1.0f)), 1e-6f);
+        const float dEdc = -k * dth / sinv;  // dE/dcos
+        float* o = tgw + 3 * (2 * p.nb + 3 * t);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float gi = dEdc * (bv[c] * inv - cosv * av[c] / aa);
+          const float gk = dEdc * (av[c] * inv - cosv * bv[c] / bb);
+          o[c] = gi; o[3 + c] = -(gi + gk); o[6 + c] = gk;
+        }
+      }
+      // PeriodicTorsionForce: k (1 + cos(n phi - phase)); slots [2 nb + 3 na + 4 t + role].  cos / sin of n phi by the
+      // angle-addition recurrence from (cos phi, sin phi) = (x, y) / |(x, y)| -- no atan2f / sinf / cosf per term; the
+      // periodicity is an integer in OpenMM; cos / sin of the phase come from the host (tors_cs)
+      for (int t = a; t < p.nt; t += n) {
+        const int i = 3 * tors_idx[4 * t], j = 3 * tors_idx[4 * t + 1], k3 = 3 * tors_idx[4 * t + 2], l = 3 * tors_idx[4 * t + 3];
+        const float per = tors_par[3 * t], k = tors_par[3 * t + 2];
+        const float cph = tors_cs[2 * t], sph = tors_cs[2 * t + 1];
+        float b1[3], b2[3], b3[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { b1[c] = xr[j + c] - xr[i + c]; b2[c] = xr[k3 + c] - xr[j + c]; b3[c] = xr[l + c] - xr[k3 + c]; }
+        const float n1[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2], b1[0] * b2[1] - b1[1] * b2[0]};
+        const float n2[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
+        const float b22 = fmaf(b2[0], b2[0], fmaf(b2[1], b2[1], b2[2] * b2[2]));
+        const float nb2 = sqrtf(b22);
+        const float yv = (b1[0] * n2[0] + b1[1] * n2[1] + b1[2] * n2[2]) * nb2;
+        const float xv = n1[0] * n2[0] + n1[1] * n2[1] + n1[2] * n2[2];
+        const float nrm = sqrtf(fmaf(xv, xv, yv * yv));
+        const float c1 = nrm > 0.f ? xv / nrm : 1.0f, s1 = nrm > 0.f ? yv / nrm : 0.0f;
+        float cn = 1.0f, sn = 0.0f;
+        const int nper = (int)per;
+        for (int q = 0; q < nper; ++q) {
+          const float cc = cn * c1 - sn * s1, ss = sn * c1 + cn * s1;
+          cn = cc; sn = ss;
+        }
+        E += k * (1.0f + (cn * cph + sn * sph));
+        const float dEdphi = -k * per * (sn * cph - cn * sph);
+        const float n11 = fmaxf(n1[0] * n1[0] + n1[1] * n1[1] + n1[2] * n1[2], 1e-20f);
+        const float n22 = fmaxf(n2[0] * n2[0] + n2[1] * n2[1] + n2[2] * n2[2], 1e-20f);
+        const float pq = (b1[0] * b2[0] + b1[1] * b2[1] + b1[2] * b2[2]) / b22;
+        const float qq = (b3[0] * b2[0] + b3[1] * b2[1] + b3[2] * b2[2]) / b22;
+        const float ci = -nb2 / n11, cl = nb2 / n22;
+        // d phi / d r of the four atoms: i: ci n1; j: -(pq + 1) ci n1 + qq cl n2; k: pq ci n1 - (qq + 1) cl n2; l: cl n2
+        const float wi[4] = {1.0f, -(pq + 1.0f), pq, 0.f}, wlc[4] = {0.f, qq, -(qq + 1.0f), 1.0f};
+        float* o = tgw + 3 * (2 * p.nb + 3 * p.na + 4 * t);
+#pragma unroll
+        for (int role = 0; role < 4; ++role)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) o[3 * role + c] = dEdphi * (wi[role] * ci * n1[c] + wlc[role] * cl * n2[c]);
+      }
+    }
+    __syncthreads();
+    if (act) {
+      const int kind_base[3] = {0, 2 * p.nb, 2 * p.nb + 3 * p.na}, arity[3] = {2, 3, 4};
+      for (int kind = 0; kind < 3; ++kind)
+        for (int e = csr_off[kind * (n + 1) + a]; e < csr_off[kind * (n + 1) + a + 1]; ++e) {
+          const int t = csr_ent[e] >> 2, role = csr_ent[e] & 3;
+          const float* o = tgw + 3 * (kind_base[kind] + arity[kind] * t + role);
+          g0 += o[0]; g1 += o[1]; g2 += o[2];
+        }
+    }
+  }
+  if (act) {
+    // ---- NonbondedForce: every partner j of atom a (exceptions carry their own parameters)
+    for (int j = 0; j < n; ++j) {
+      if (j == a) continue;
+      const int lo = a < j ? a : j, hi = a < j ? j : a;
+      const int t = lo * n - lo * (lo + 1) / 2 + (hi - lo - 1);
+      const float qq = pair_par[4 * t], sg = pair_par[4 * t + 1], e4 = pair_par[4 * t + 2], exc = pair_par[4 * t + 3];
+      const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
+      const float r2 = fmaf(d0, d0, fmaf(d1, d1, d2 * d2));
+      const float ir2 = 1.0f / r2, ir = sqrtf(ir2);
+      const float s2 = sg * sg * ir2, s6 = s2 * s2 * s2;
+      float e = e4 * fmaf(s6, s6, -s6);
+      float g = e4 * (-12.0f * s6 * s6 + 6.0f * s6) * ir2;  // (dE/dr)/r
+      if (p.use_cutoff && exc == 0.f) {
+        e += qq * (ir + p.krf * r2 - p.crf);
+        g += qq * (-ir * ir2 + 2.0f * p.krf);
+      } else {
+        e += qq * ir;
+        g += -qq * ir * ir2;
+      }
+      const float inside = (!p.use_cutoff || r2 < p.cutoff * p.cutoff) ? 1.0f : 0.0f;
+      if (a < j) E += inside * e;
+      g *= inside;
+      g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
+    }
+  }
+  // ---- GBSAOBCForce, OBC1 (Onufriev-Bashford-Case 2004, model I: alpha, beta, gamma = 0.8, 0, 2.909125) with the
+  //      ACE surface-area term, as in OpenMM's reference algorithm: Born radii from the pairwise HCT integral,
+  //      the generalised-Born pair sum (self terms included), then the chain rule through the Born radii.
+  if (p.gb) {
+    const float rc = p.use_cutoff ? p.cutoff : 3.0e38f;
+    const float rho = gb_par[4 * a], sga = gb_par[4 * a + 1], R = gb_par[4 * a + 2], qa = gb_par[4 * a + 3];
+    float chain = 0.f, Ba = 1.f;
+    if (act) {
+      float sum = 0.f;
+      for (int j = 0; j < n; ++j) {  // HCT integral of atom a
+        if (j == a) continue;
+        const float sg = gb_par[4 * j + 1];
+        const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
+        const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2)));
+        const float rs = r + sg, ir = 1.0f / r;
+        const float l = 1.0f / fmaxf(rho, fabsf(r - sg)), u = 1.0f / rs;
+        const float l2 = l * l, u2 = u * u;
+        float term = l - u + 0.25f * r * (u2 - l2) + 0.5f * ir * logf(u / l) + 0.25f * sg * sg * ir * (l2 - u2);
+        if (rho < sg - r) term += 2.0f * (1.0f / rho - l);
+        sum += (rho < rs && r < rc) ? term : 0.f;
+      }
+      const float psi = 0.5f * rho * sum, psi2 = psi * psi;
+      const float th = tanhf(fmaf(2.909125f * psi2, psi, 0.8f * psi));
+      Ba = 1.0f / (1.0f / rho - th / R);
+      chain = Ba * Ba * (1.0f - th * th) * fmaf(3.0f * 2.909125f, psi2, 0.8f) * 0.5f * rho / R;  // dB / d(sum)
+      br[wl * n + a] = Ba;
+    }
+    __syncthreads();
+    if (act) {
+      // self term and ACE surface area, then the generalised-Born pair sum
+      const float rr = R + p.gb_probe, q3 = (R / Ba) * (R / Ba) * (R / Ba);
+      const float sa = p.gb_sa * rr * rr * q3 * q3;
+      const float eself = 0.5f * p.gb_pf * qa * qa / Ba;
+      E += eself + sa;
+      float bfa = -(eself + 6.0f * sa) / Ba;  // dE/dB_a
+      for (int j = 0; j < n; ++j) {
+        if (j == a) continue;
+        const float c = p.gb_pf * qa * gb_par[4 * j + 3], Bj = br[wl * n + j];
+        const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
+        const float r2 = fmaf(d0, d0, fmaf(d1, d1, d2 * d2));
+        const float a2 = Ba * Bj, Dv = r2 / (4.0f * a2), ex = expf(-Dv);
+        const float if2 = 1.0f / fmaf(a2, ex, r2), G = c * sqrtf(if2);
+        const float inside = (r2 < rc * rc) ? 1.0f : 0.f;
+        if (a < j) E += inside * (p.use_cutoff ? G - c / p.cutoff : G);
+        const float g = inside * (-G * if2 * (1.0f - 0.25f * ex));           // (dG/dr)/r
+        bfa = fmaf(inside * (-0.5f * G * if2 * ex * (1.0f + Dv)), Bj, bfa);  // dG/d(Ba Bj) * Bj
+        g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
+      }
+      bw[wl * n + a] = bfa * chain;  // dE / d(sum_a)
+    }
+    __syncthreads();
+    if (act) {
+      const float wa = bw[wl * n + a];
+      for (int j = 0; j < n; ++j) {  // chain rule through the Born radii of a (descreened by j) and of j (by a)
+        if (j == a) continue;
+        const float rhoj = gb_par[4 * j], sgj = gb_par[4 * j + 1], wj = bw[wl * n + j];
+        const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
+        const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2))), ir = 1.0f / r;
+        float acc = 0.f;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+          const float ro = side ? rhoj : rho, sg = side ? sga : sgj, w = side ? wj : wa;
+          const float rs = r + sg, dl = r - sg;
+          const float l = 1.0f / fmaxf(ro, fabsf(dl)), u = 1.0f / rs;
+          const float l2 = l * l, u2 = u * u, u3 = u2 * u;
+          const float lp = (fabsf(dl) > ro) ? (dl > 0.f ? -l2 : l2) : 0.f;  // dl/dr
+          const float lg = logf(u / l);
+          float dt = lp + u2 + 0.25f * (u2 - l2) - 0.5f * r * fmaf(l, lp, u3) - 0.5f * lg * ir * ir -
+                     0.5f * ir * (u + lp / l) - 0.25f * sg * sg * (l2 - u2) * ir * ir + 0.5f * sg * sg * ir * fmaf(l, lp, u3);
+          if (ro < sg - r) dt -= 2.0f * lp;
+          acc += (ro < rs && r < rc) ? w * dt : 0.f;
+        }
+        const float g = acc * ir;
+        g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
+      }
+    }
+  }
+  E_out = E; g0_out = g0; g1_out = g1; g2_out = g2;
+}
+
 template <bool DESCENT>
 __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
   extern __shared__ float sm[];
   const int n = p.n, D = 3 * n, WPB = p.wpb;
-  // interaction tables: LDS-resident for the whole (persistent) block
-  unsigned* tb = reinterpret_cast<unsigned*>(sm);
-  for (int i = threadIdx.x; i < p.blob_words; i += FF_THREADS) tb[i] = p.blob[i];
-  const int* bond_idx = reinterpret_cast<const int*>(tb + p.o_bond_idx);
-  const float* bond_par = reinterpret_cast<const float*>(tb + p.o_bond_par);
-  const int* angle_idx = reinterpret_cast<const int*>(tb + p.o_angle_idx);
-  const float* angle_par = reinterpret_cast<const float*>(tb + p.o_angle_par);
-  const int* tors_idx = reinterpret_cast<const int*>(tb + p.o_tors_idx);
-  const float* tors_par = reinterpret_cast<const float*>(tb + p.o_tors_par);
-  const float* tors_cs = reinterpret_cast<const float*>(tb + p.o_tors_cs);  // [nt][2] cos, sin of the phase
-  const float* pair_par = reinterpret_cast<const float*>(tb + p.o_pair_par);
-  const float* gb_par = reinterpret_cast<const float*>(tb + p.o_gb_par);
-  const int* csr_off = reinterpret_cast<const int*>(tb + p.o_csr_off);  // [3][n+1]: bonds, angles, torsions
-  const int* csr_ent = reinterpret_cast<const int*>(tb + p.o_csr_ent);  // (term << 2) | role
-  float* xs = sm + p.blob_words;   // [WPB][D] coordinates (nm)
-  float* gs = xs + WPB * D;        // [WPB][D] gradient, for the coalesced store
-  float* es = gs + WPB * D;        // [WPB][n] energy partials
-  float* br = es + WPB * n;        // [WPB][n] Born radii
-  float* bw = br + WPB * n;        // [WPB][n] dE/d(HCT sum)
-  const int n_slots = 2 * p.nb + 3 * p.na + 4 * p.nt;  // gradient slots of the bonded terms: one per (term, participating atom)
-  float* tg = bw + WPB * n;        // [WPB][n_slots][3] bonded-term gradients, phase 1 -> phase 2
-  float* xu = tg + WPB * 3 * n_slots;  // DESCENT: [WPB][D] walkers in model units, resident over the steps
-  float* vv = xu + WPB * D;        // DESCENT: [WPB][D] updated walkers before the centring
+  const FfLds L = ff_stage(p, sm);
+  float *xs = L.xs, *gs = L.gs, *es = L.es, *xu = L.xu, *vv = L.vv;
   const int tid = threadIdx.x, wl = tid / n, a = tid - wl * n;
   const bool lane_on = wl < WPB;
   const long long nblk = (p.B + WPB - 1) / WPB;
@@ -90,208 +325,8 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
     for (int q = tid; q < nw * D; q += FF_THREADS) xs[q] = (DESCENT ? xu[q] : p.x[w0 * D + q]) * p.length_scale;
     __syncthreads();
     const bool act = lane_on && wl < nw;
-    const float* xr = xs + (act ? wl : 0) * D;
-    const float xa0 = xr[3 * a % D], xa1 = xr[(3 * a + 1) % D], xa2 = xr[(3 * a + 2) % D];
-    float E = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f;
-    // ---- bonded terms, two phases (round 6).  Phase 1: one thread per TERM (the walker's threads deal the bonds, angles and
-    //      torsions out among themselves) evaluates it ONCE and parks the gradient of every participating atom in LDS;
-    //      phase 2: one thread per ATOM adds up its slots through the per-atom lists.  Before, every participating atom
-    //      re-evaluated the whole term (angles 3x, torsions 4x, with acosf / atan2f / sinf / cosf each time) and the atom
-    //      sitting in the most torsions set the pace of its wave.
-    {
-      float* tgw = tg + (act ? wl : 0) * (3 * n_slots);
-      if (act) {
-        // HarmonicBondForce: 1/2 k (r - r0)^2; slots [2 t + role]
-        for (int t = a; t < p.nb; t += n) {
-          const int i = 3 * bond_idx[2 * t], j = 3 * bond_idx[2 * t + 1];
-          const float r0 = bond_par[2 * t], k = bond_par[2 * t + 1];
-          const float d0 = xr[i] - xr[j], d1 = xr[i + 1] - xr[j + 1], d2 = xr[i + 2] - xr[j + 2];
-          const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2)));
-          const float dr = r - r0;
-          E = fmaf(0.5f * k * dr, dr, E);
-          const float c = k * dr / r;
-          float* o = tgw + 3 * (2 * t);
-          o[0] = c * d0; o[1] = c * d1; o[2] = c * d2;
-          o[3] = -c * d0; o[4] = -c * d1; o[5] = -c * d2;
-        }
-        // HarmonicAngleForce: 1/2 k (theta - theta0)^2; slots [2 nb + 3 t + role]
-        for (int t = a; t < p.na; t += n) {
-          const int i = 3 * angle_idx[3 * t], j = 3 * angle_idx[3 * t + 1], k3 = 3 * angle_idx[3 * t + 2];
-          const float th0 = angle_par[2 * t], k = angle_par[2 * t + 1];
-          float av[3], bv[3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) { av[c] = xr[i + c] - xr[j + c]; bv[c] = xr[k3 + c] - xr[j + c]; }
-          const float aa = fmaf(av[0], av[0], fmaf(av[1], av[1], av[2] * av[2]));
-          const float bb = fmaf(bv[0], bv[0], fmaf(bv[1], bv[1], bv[2] * bv[2]));
-          const float ab = fmaf(av[0], bv[0], fmaf(av[1], bv[1], av[2] * bv[2]));
-          const float inv = 1.0f / sqrtf(aa * bb);
-          const float cosv = fminf(fmaxf(ab * inv, -1.0f), 1.0f);
-          const float dth = acosf(cosv) - th0;
-          E = fmaf(0.5f * k * dth, dth, E);
-          const float sinv = fmaxf(sqrtf(fmaf(-cosv, cosv, 1.0f)), 1e-6f);
-          const float dEdc = -k * dth / sinv;  // dE/dcos
-          float* o = tgw + 3 * (2 * p.nb + 3 * t);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float gi = dEdc * (bv[c] * inv - cosv * av[c] / aa);
-            const float gk = dEdc * (av[c] * inv - cosv * bv[c] / bb);
-            o[c] = gi; o[3 + c] = -(gi + gk); o[6 + c] = gk;
-          }
-        }
-        // PeriodicTorsionForce: k (1 + cos(n phi - phase)); slots [2 nb + 3 na + 4 t + role].  cos / sin of n phi by the
-        // angle-addition recurrence from (cos phi, sin phi) = (x, y) / |(x, y)| -- no atan2f / sinf / cosf per term; the
-        // periodicity is an integer in OpenMM; cos / sin of the phase come from the host (tors_cs)
-        for (int t = a; t < p.nt; t += n) {
-          const int i = 3 * tors_idx[4 * t], j = 3 * tors_idx[4 * t + 1], k3 = 3 * tors_idx[4 * t + 2], l = 3 * tors_idx[4 * t + 3];
-          const float per = tors_par[3 * t], k = tors_par[3 * t + 2];
-          const float cph = tors_cs[2 * t], sph = tors_cs[2 * t + 1];
-          float b1[3], b2[3], b3[3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) { b1[c] = xr[j + c] - xr[i + c]; b2[c] = xr[k3 + c] - xr[j + c]; b3[c] = xr[l + c] - xr[k3 + c]; }
-          const float n1[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2], b1[0] * b2[1] - b1[1] * b2[0]};
-          const float n2[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
-          const float b22 = fmaf(b2[0], b2[0], fmaf(b2[1], b2[1], b2[2] * b2[2]));
-          const float nb2 = sqrtf(b22);
-          const float yv = (b1[0] * n2[0] + b1[1] * n2[1] + b1[2] * n2[2]) * nb2;
-          const float xv = n1[0] * n2[0] + n1[1] * n2[1] + n1[2] * n2[2];
-          const float nrm = sqrtf(fmaf(xv, xv, yv * yv));
-          const float c1 = nrm > 0.f ? xv / nrm : 1.0f, s1 = nrm > 0.f ? yv / nrm : 0.0f;
-          float cn = 1.0f, sn = 0.0f;
-          const int nper = (int)per;
-          for (int q = 0; q < nper; ++q) {
-            const float cc = cn * c1 - sn * s1, ss = sn * c1 + cn * s1;
-            cn = cc; sn = ss;
-          }
-          E += k * (1.0f + (cn * cph + sn * sph));
-          const float dEdphi = -k * per * (sn * cph - cn * sph);
-          const float n11 = fmaxf(n1[0] * n1[0] + n1[1] * n1[1] + n1[2] * n1[2], 1e-20f);
-          const float n22 = fmaxf(n2[0] * n2[0] + n2[1] * n2[1] + n2[2] * n2[2], 1e-20f);
-          const float pq = (b1[0] * b2[0] + b1[1] * b2[1] + b1[2] * b2[2]) / b22;
-          const float qq = (b3[0] * b2[0] + b3[1] * b2[1] + b3[2] * b2[2]) / b22;
-          const float ci = -nb2 / n11, cl = nb2 / n22;
-          // d phi / d r of the four atoms: i: ci n1; j: -(pq + 1) ci n1 + qq cl n2; k: pq ci n1 - (qq + 1) cl n2; l: cl n2
-          const float wi[4] = {1.0f, -(pq + 1.0f), pq, 0.f}, wlc[4] = {0.f, qq, -(qq + 1.0f), 1.0f};
-          float* o = tgw + 3 * (2 * p.nb + 3 * p.na + 4 * t);
-#pragma unroll
-          for (int role = 0; role < 4; ++role)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[3 * role + c] = dEdphi * (wi[role] * ci * n1[c] + wlc[role] * cl * n2[c]);
-        }
-      }
-      __syncthreads();
-      if (act) {
-        const int kind_base[3] = {0, 2 * p.nb, 2 * p.nb + 3 * p.na}, arity[3] = {2, 3, 4};
-        for (int kind = 0; kind < 3; ++kind)
-          for (int e = csr_off[kind * (n + 1) + a]; e < csr_off[kind * (n + 1) + a + 1]; ++e) {
-            const int t = csr_ent[e] >> 2, role = csr_ent[e] & 3;
-            const float* o = tgw + 3 * (kind_base[kind] + arity[kind] * t + role);
-            g0 += o[0]; g1 += o[1]; g2 += o[2];
-          }
-      }
-    }
-    if (act) {
-      // ---- NonbondedForce: every partner j of atom a (exceptions carry their own parameters)
-      for (int j = 0; j < n; ++j) {
-        if (j == a) continue;
-        const int lo = a < j ? a : j, hi = a < j ? j : a;
-        const int t = lo * n - lo * (lo + 1) / 2 + (hi - lo - 1);
-        const float qq = pair_par[4 * t], sg = pair_par[4 * t + 1], e4 = pair_par[4 * t + 2], exc = pair_par[4 * t + 3];
-        const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
-        const float r2 = fmaf(d0, d0, fmaf(d1, d1, d2 * d2));
-        const float ir2 = 1.0f / r2, ir = sqrtf(ir2);
-        const float s2 = sg * sg * ir2, s6 = s2 * s2 * s2;
-        float e = e4 * fmaf(s6, s6, -s6);
-        float g = e4 * (-12.0f * s6 * s6 + 6.0f * s6) * ir2;  // (dE/dr)/r
-        if (p.use_cutoff && exc == 0.f) {
-          e += qq * (ir + p.krf * r2 - p.crf);
-          g += qq * (-ir * ir2 + 2.0f * p.krf);
-        } else {
-          e += qq * ir;
-          g += -qq * ir * ir2;
-        }
-        const float inside = (!p.use_cutoff || r2 < p.cutoff * p.cutoff) ? 1.0f : 0.0f;
-        if (a < j) E += inside * e;
-        g *= inside;
-        g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
-      }
-    }
-    // ---- GBSAOBCForce, OBC1 (Onufriev-Bashford-Case 2004, model I: alpha, beta, gamma = 0.8, 0, 2.909125) with the
-    //      ACE surface-area term, as in OpenMM's reference algorithm: Born radii from the pairwise HCT integral,
-    //      the generalised-Born pair sum (self terms included), then the chain rule through the Born radii.
-    if (p.gb) {
-      const float rc = p.use_cutoff ? p.cutoff : 3.0e38f;
-      const float rho = gb_par[4 * a], sga = gb_par[4 * a + 1], R = gb_par[4 * a + 2], qa = gb_par[4 * a + 3];
-      float chain = 0.f, Ba = 1.f;
-      if (act) {
-        float sum = 0.f;
-        for (int j = 0; j < n; ++j) {  // HCT integral of atom a
-          if (j == a) continue;
-          const float sg = gb_par[4 * j + 1];
-          const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
-          const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2)));
-          const float rs = r + sg, ir = 1.0f / r;
-          const float l = 1.0f / fmaxf(rho, fabsf(r - sg)), u = 1.0f / rs;
-          const float l2 = l * l, u2 = u * u;
-          float term = l - u + 0.25f * r * (u2 - l2) + 0.5f * ir * logf(u / l) + 0.25f * sg * sg * ir * (l2 - u2);
-          if (rho < sg - r) term += 2.0f * (1.0f / rho - l);
-          sum += (rho < rs && r < rc) ? term : 0.f;
-        }
-        const float psi = 0.5f * rho * sum, psi2 = psi * psi;
-        const float th = tanhf(fmaf(2.909125f * psi2, psi, 0.8f * psi));
-        Ba = 1.0f / (1.0f / rho - th / R);
-        chain = Ba * Ba * (1.0f - th * th) * fmaf(3.0f * 2.909125f, psi2, 0.8f) * 0.5f * rho / R;  // dB / d(sum)
-        br[wl * n + a] = Ba;
-      }
-      __syncthreads();
-      if (act) {
-        // self term and ACE surface area, then the generalised-Born pair sum
-        const float rr = R + p.gb_probe, q3 = (R / Ba) * (R / Ba) * (R / Ba);
-        const float sa = p.gb_sa * rr * rr * q3 * q3;
-        const float eself = 0.5f * p.gb_pf * qa * qa / Ba;
-        E += eself + sa;
-        float bfa = -(eself + 6.0f * sa) / Ba;  // dE/dB_a
-        for (int j = 0; j < n; ++j) {
-          if (j == a) continue;
-          const float c = p.gb_pf * qa * gb_par[4 * j + 3], Bj = br[wl * n + j];
-          const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
-          const float r2 = fmaf(d0, d0, fmaf(d1, d1, d2 * d2));
-          const float a2 = Ba * Bj, Dv = r2 / (4.0f * a2), ex = expf(-Dv);
-          const float if2 = 1.0f / fmaf(a2, ex, r2), G = c * sqrtf(if2);
-          const float inside = (r2 < rc * rc) ? 1.0f : 0.f;
-          if (a < j) E += inside * (p.use_cutoff ? G - c / p.cutoff : G);
-          const float g = inside * (-G * if2 * (1.0f - 0.25f * ex));           // (dG/dr)/r
-          bfa = fmaf(inside * (-0.5f * G * if2 * ex * (1.0f + Dv)), Bj, bfa);  // dG/d(Ba Bj) * Bj
-          g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
-        }
-        bw[wl * n + a] = bfa * chain;  // dE / d(sum_a)
-      }
-      __syncthreads();
-      if (act) {
-        const float wa = bw[wl * n + a];
-        for (int j = 0; j < n; ++j) {  // chain rule through the Born radii of a (descreened by j) and of j (by a)
-          if (j == a) continue;
-          const float rhoj = gb_par[4 * j], sgj = gb_par[4 * j + 1], wj = bw[wl * n + j];
-          const float d0 = xa0 - xr[3 * j], d1 = xa1 - xr[3 * j + 1], d2 = xa2 - xr[3 * j + 2];
-          const float r = sqrtf(fmaf(d0, d0, fmaf(d1, d1, d2 * d2))), ir = 1.0f / r;
-          float acc = 0.f;
-#pragma unroll
-          for (int side = 0; side < 2; ++side) {
-            const float ro = side ? rhoj : rho, sg = side ? sga : sgj, w = side ? wj : wa;
-            const float rs = r + sg, dl = r - sg;
-            const float l = 1.0f / fmaxf(ro, fabsf(dl)), u = 1.0f / rs;
-            const float l2 = l * l, u2 = u * u, u3 = u2 * u;
-            const float lp = (fabsf(dl) > ro) ? (dl > 0.f ? -l2 : l2) : 0.f;  // dl/dr
-            const float lg = logf(u / l);
-            float dt = lp + u2 + 0.25f * (u2 - l2) - 0.5f * r * fmaf(l, lp, u3) - 0.5f * lg * ir * ir -
-                       0.5f * ir * (u + lp / l) - 0.25f * sg * sg * (l2 - u2) * ir * ir + 0.5f * sg * sg * ir * fmaf(l, lp, u3);
-            if (ro < sg - r) dt -= 2.0f * lp;
-            acc += (ro < rs && r < rc) ? w * dt : 0.f;
-          }
-          const float g = acc * ir;
-          g0 = fmaf(g, d0, g0); g1 = fmaf(g, d1, g1); g2 = fmaf(g, d2, g2);
-        }
-      }
-    }
+    float E, g0, g1, g2;
+    ff_eval(p, L, act, wl, a, E, g0, g1, g2);
     if (act) {
       const float sc = -p.inv_kT * p.length_scale;  // d logp / d x_model
       gs[wl * D + 3 * a] = sc * g0; gs[wl * D + 3 * a + 1] = sc * g1; gs[wl * D + 3 * a + 2] = sc * g2;
@@ -348,12 +383,162 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
   }
 }
 
+// ---------------------------------------------------------------------------- fused MALA chain (pita_ff_mala)
+// metropolis_hastings_mala(_adaptive) (sde_integration.py:28-45,362-470) with the mapping of ff_kernel<true>: a thread owns
+// its (walker, atom) over all steps of the launch, x / F / x' of the atom stay in registers, the walker in LDS.  Per step:
+// F at x, proposal x' = (x + dt/2 F) + sqrt(dt) xi, logp' and F' at x', log q_f / log q_b, accept iff
+// log u < (logp' - logp) + (log q_b - log q_f), the reference's float blend, optional centring.  Proposal and accept are
+// the arithmetic of mala_propose_kernel / mala_accept_kernel (sampler_kernels.hip) op for op and in their summation
+// orders, the two evaluations are ff_eval as pita_ff_logp_force runs it: the chain equals the launch-per-kernel chain bit
+// for bit.  The LDS footprint is the descent's: xu, vv as there, gs (free here: F stays in registers) holds the per-atom
+// partials of log q_f, log q_b and the accept flags.
+// No grid-wide barrier and no wait of any kind: the only cross-block traffic is one integer atomicAdd of the accepted
+// walkers per tile and step.  A non-adaptive chain is ONE launch (tiles outside, steps inside); an adaptive chain is one
+// launch per step (stream order is the barrier), each deriving its step size from dt_dev[0] and the counts of the
+// steps before it -- the replay loop of mala_finish_kernel (energy_kernels.hip), which runs last and leaves the rates
+// and the final step size.
+struct FfMalaParams {
+  float* x;                  // [B][3 n] walkers, updated in place
+  float* logp;               // [B] log-density of x, carried
+  const float* noise;        // nullable [n_steps][B][3 n]
+  const float* uniforms;     // nullable [n_steps][B]
+  const long long* walker_ids;  // nullable [B] Philox keys of the walkers
+  unsigned long long seed, walker_offset;
+  long long step0, total, B;
+  const double* dt_dev;      // step size on entry of the CHAIN (not written by this kernel)
+  unsigned long long* sync;  // [n_steps + 1] accepted walkers per step (low 32 bits, the layout launch_mala_finish reads)
+  int step_base, steps;      // this launch runs steps [step_base, step_base + steps) of the chain
+  int adaptive, remove_mean;
+};
+
+__global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaParams q) {
+  extern __shared__ float sm[];
+  const int n = p.n, D = 3 * n, WPB = p.wpb;
+  const FfLds L = ff_stage(p, sm);
+  float *xs = L.xs, *es = L.es, *xu = L.xu, *vv = L.vv;
+  float *qf = L.gs, *qb = qf + WPB * n, *flag = qb + WPB * n;  // [WPB][n] partial |x' - fwd mean|^2, |x - bwd mean|^2; [WPB] 1.0 = accepted
+  const int tid = threadIdx.x, wl = tid / n, a = tid - wl * n;
+  const bool lane_on = wl < WPB;
+  // step size of step `step_base`: constant, or adapted on the acceptance rates of the steps before (mala_adapt_kernel's rule)
+  double dtd = q.dt_dev[0];
+  if (q.adaptive)
+    for (int s = 0; s < q.step_base; ++s) {
+      const float rate = (float)(int)(q.sync[s] & 0xFFFFFFFFull) / (float)q.total;
+      dtd = ((double)rate > 0.55) ? dtd * 1.1 : dtd / 1.1;  // sde_integration.py:439-443
+    }
+  const float hdt = (float)(0.5 * dtd), sdt = (float)sqrt(dtd), tdt = (float)(2.0 * dtd);
+  const float sc = -p.inv_kT * p.length_scale;  // d logp / d x_model
+  const long long nblk = (q.B + WPB - 1) / WPB;
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const long long w0 = blk * WPB;
+    const int nw = (int)((q.B - w0) < WPB ? (q.B - w0) : WPB);
+    for (int i = tid; i < nw * D; i += FF_THREADS) xu[i] = q.x[w0 * D + i];
+    __syncthreads();
+    const bool act = lane_on && wl < nw;
+    const long long wg = w0 + (act ? wl : 0);
+    const unsigned long long key = q.walker_ids ? (unsigned long long)q.walker_ids[wg] : q.walker_offset + (unsigned long long)wg;
+    float lp = (act && a == 0) ? q.logp[wg] : 0.f;
+    for (int st = 0; st < q.steps; ++st) {
+      const int s = q.step_base + st;
+      // ---- F at x
+      for (int i = tid; i < nw * D; i += FF_THREADS) xs[i] = xu[i] * p.length_scale;
+      __syncthreads();
+      float E, g0, g1, g2;
+      ff_eval(p, L, act, wl, a, E, g0, g1, g2);
+      float xo[3] = {0.f, 0.f, 0.f}, xp[3] = {0.f, 0.f, 0.f};
+      if (act) {
+        // ---- proposal and the atom's share of log q_f
+        const float F[3] = {sc * g0, sc * g1, sc * g2};
+        float xi[4] = {0.f, 0.f, 0.f, 0.f};
+        if (q.noise) {
+          const long long base = (((long long)s * q.B + wg) * n + a) * 3;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) xi[k] = q.noise[base + k];
+        } else {
+          philox_normal4(q.seed, key, q.step0 + s, (uint32_t)a, xi);
+        }
+        float sf = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          xo[k] = xu[wl * D + 3 * a + k];
+          xp[k] = (xo[k] + hdt * F[k]) + sdt * xi[k];
+          vv[wl * D + 3 * a + k] = xp[k];
+          const float df = xp[k] - (xo[k] + hdt * F[k]);
+          sf += df * df;
+        }
+        qf[wl * n + a] = sf;
+      }
+      __syncthreads();
+      // ---- logp', F' at x'
+      for (int i = tid; i < nw * D; i += FF_THREADS) xs[i] = vv[i] * p.length_scale;
+      __syncthreads();
+      ff_eval(p, L, act, wl, a, E, g0, g1, g2);
+      if (act) {
+        const float Fp[3] = {sc * g0, sc * g1, sc * g2};
+        float sb = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float db = xo[k] - (xp[k] + hdt * Fp[k]);
+          sb += db * db;
+        }
+        qb[wl * n + a] = sb;
+        es[wl * n + a] = E;
+      }
+      __syncthreads();
+      // ---- accept / reject: one thread per walker, sums in atom order
+      if (act && a == 0) {
+        float tot = 0.f, sf = 0.f, sb = 0.f;
+        for (int j = 0; j < n; ++j) tot += es[wl * n + j];
+        for (int j = 0; j < n; ++j) { sf += qf[wl * n + j]; sb += qb[wl * n + j]; }
+        const float lpp = -tot * p.inv_kT;
+        const float lqf = -sf / tdt, lqb = -sb / tdt;
+        const float ratio = (lpp - lp) + (lqb - lqf);
+        const float u = q.uniforms ? q.uniforms[(long long)s * q.B + wg] : philox_uniform(q.seed, key, q.step0 + s, 0xFFFFFu);
+        const float af = (logf(u) < ratio) ? 1.0f : 0.0f;
+        lp = af * lpp + (1.0f - af) * lp;
+        flag[wl] = af;
+      }
+      __syncthreads();
+      float v[3] = {0.f, 0.f, 0.f};
+      if (act) {
+        const float af = flag[wl];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          v[k] = af * xp[k] + (1.0f - af) * xo[k];
+          vv[wl * D + 3 * a + k] = v[k];
+        }
+      }
+      if (tid == 0) {  // integer add: the step's count does not depend on the order of the blocks
+        int c = 0;
+        for (int j = 0; j < nw; ++j) c += flag[j] != 0.f;
+        if (c) atomicAdd(&q.sync[s], (unsigned long long)c);
+      }
+      __syncthreads();
+      if (act) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (q.remove_mean) {
+            float sum = 0.f;
+            for (int j = 0; j < n; ++j) sum += vv[wl * D + 3 * j + k];
+            v[k] -= sum / (float)n;
+          }
+          xu[wl * D + 3 * a + k] = v[k];
+        }
+      }
+      __syncthreads();
+    }  // steps
+    for (int i = tid; i < nw * D; i += FF_THREADS) q.x[w0 * D + i] = xu[i];
+    if (act && a == 0) q.logp[wg] = lp;
+    __syncthreads();
+  }
+}
+
 }  // namespace pita
 
 struct pita_ff {
   pita::FfParams p{};
   void* d_all = nullptr;
-  size_t lds_logp = 0, lds_descent = 0;  // dynamic LDS bytes per block of the two entry points at p.wpb walkers
+  size_t lds_logp = 0, lds_descent = 0;  // dynamic LDS bytes per block at p.wpb walkers (pita_ff_mala runs in lds_descent)
 };
 
 using namespace pita;
@@ -447,8 +632,9 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     tcs[2 * t + 1] = (float)sin((double)c->tors_par[3 * t + 1]);
   }
   const size_t total = b_bi + b_bp + b_ai + b_ap + b_ti + b_tp + b_tc + b_pi + b_pp + b_gb + b_co + b_ce + 16 * 12;  // each table padded to 16 B
-  // Launch plan, shared by both entry points: floor(256/n) walkers per block where the LDS holds them, fewer where it
-  // does not.  Sized for the descent kernel (the larger footprint), so a handle that exists is taken by both.
+  // Launch plan, shared by all entry points: floor(256/n) walkers per block where the LDS holds them, fewer where it
+  // does not.  Sized for the descent kernel (the larger footprint; the MALA chain lives in the same), so a handle that
+  // exists is taken by all of them.
   auto pad16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   const size_t blob_bytes = pad16(b_bi) + pad16(b_bp) + pad16(b_ai) + pad16(b_ap) + pad16(b_ti) + pad16(b_tp) + pad16(b_tc) +
                             pad16(b_pi) + pad16(b_pp) + pad16(b_gb) + pad16(b_co) + pad16(b_ce);
@@ -562,4 +748,38 @@ extern "C" int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise, int6
                      (hipStream_t)stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
+}
+
+extern "C" size_t pita_ff_mala_workspace_bytes(int n_steps) { return 8 * (size_t)((n_steps > 0 ? n_steps : 0) + 1); }
+
+extern "C" int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* noise, const float* uniforms, int64_t B,
+                            int n_steps, double* dt_dev, int adaptive, int64_t total, uint64_t seed, uint64_t walker_offset,
+                            const int64_t* walker_ids, int64_t step0, int remove_mean, float* rates_out, void* workspace,
+                            void* stream) {
+  PITA_REQUIRE(ff && dt_dev && workspace, "pita_ff_mala: null argument (handle, dt_dev, workspace)");
+  PITA_REQUIRE(B >= 0 && n_steps >= 0 && total > 0, "pita_ff_mala: bad argument (B >= 0, n_steps >= 0, total > 0)");
+  PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_ff_mala: workspace must be 8-byte aligned");
+  if (B == 0 || n_steps == 0) return PITA_OK;
+  PITA_REQUIRE(x && logp, "pita_ff_mala: null argument (x, logp)");
+  hipStream_t s = (hipStream_t)stream;
+  FfParams p = ff->p;  // the plan of pita_ff_descent: the chain lives in the descent's LDS footprint
+  FfMalaParams q{};
+  q.x = x; q.logp = logp; q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids;
+  q.seed = seed; q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.B = B; q.dt_dev = dt_dev;
+  q.sync = static_cast<unsigned long long*>(workspace);
+  q.adaptive = adaptive ? 1 : 0; q.remove_mean = remove_mean;
+  PITA_HIP_CHECK(hipMemsetAsync(q.sync, 0, pita_ff_mala_workspace_bytes(n_steps), s));
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_mala_kernel), ff->lds_descent));
+  const long long nblk = (B + p.wpb - 1) / p.wpb;
+  const long long cap = 256LL * 8;
+  const dim3 grid((unsigned)(nblk < cap ? nblk : cap));
+  // non-adaptive: the whole chain in one launch; adaptive: one launch per step, each reads the counts of the steps before
+  const int launches = adaptive ? n_steps : 1;
+  q.steps = adaptive ? 1 : n_steps;
+  for (int l = 0; l < launches; ++l) {
+    q.step_base = l;
+    hipLaunchKernelGGL(ff_mala_kernel, grid, dim3(FF_THREADS), ff->lds_descent, s, p, q);
+    PITA_LAUNCH_CHECK();
+  }
+  return launch_mala_finish(dt_dev, q.sync, n_steps, (long long)total, adaptive, rates_out, stream);
 }
