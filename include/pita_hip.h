@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PITA_ABI_VERSION 12
+#define PITA_ABI_VERSION 13
 
 enum {
   PITA_OK = 0,
@@ -176,6 +176,15 @@ int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const float* x, co
 int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta /*nullable*/,
                        const float* cot /*nullable*/, float* out /*nullable*/, float* vjp, float* dot_h /*nullable*/,
                        int64_t B, void* stream);
+
+/* trace(J_x D)(h, x) of the EDM denoiser around the wide backbone and, optionally, D itself: ONE call
+ * (replaces n*d pita_egnn_wide_jvp launches, utils.py:30-51); bit-identical to them.  One launch whose work items are
+ * (walker, unit direction) pairs -- the matrix-pipe kernel where the particle system has one, the vector-pipe kernel on
+ * exactly the items it flagged (and on all items otherwise, or under PITA_WIDE_NO_MFMA) -- writes the diagonal entries
+ * dD[b, dir] to a handle-owned scratch; a reduction adds them per walker in direction order. */
+int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float* h, const float* x,
+                                  const float* beta /*nullable*/, float* trace /*[B]*/,
+                                  float* denoiser_out /*nullable [B, n*d]*/, int64_t B, void* stream);
 
 /* Diagonal Gaussian mixture with equal weights.
  * replaces GMM.__call__ (pita/src/energies/gmm_energy.py:87-90) ->

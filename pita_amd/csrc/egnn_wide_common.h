@@ -19,8 +19,10 @@ struct pita_egnn_wide {
   void* d_bk = nullptr;
   size_t bk_bytes = 0;
   int* d_flag = nullptr;  // set by the matrix-pipe kernel when a walker comes out non-finite: the repair pass returns at once otherwise
-  int* d_jbad = nullptr;    // [B] flags of the matrix-pipe forward-mode kernel (walkers left to the vector-pipe kernel)
-  size_t jbad_bytes = 0;
+  int* d_jbad = nullptr;    // [B] flags of the matrix-pipe forward-mode kernel (walkers left to the vector-pipe kernel);
+  size_t jbad_bytes = 0;    // [B * n*d], one per (walker, direction) item, in pita_egnn_wide_jacobian_trace
+  float* d_jdiag = nullptr;  // pita_egnn_wide_jacobian_trace: [n*d, B] diagonal entries dD[b, dir] before the reduction
+  size_t jdiag_bytes = 0;
   float* d_vjp_ws = nullptr;  // reverse-mode kernel (vector pipe): per-wave checkpoints of the forward sweep
   size_t vjp_ws_bytes = 0;
 };
@@ -40,5 +42,9 @@ int wide64_sampler(pita_egnn_wide* net, float* x, long long B, const float* step
 int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* vx, int dir,
                const float* vh, float* out, float* dout, float* dot_out, long long dot_stride, long long dot_off,
                float* diag_acc, int* bad, long long B, hipStream_t stream);
+// the same over all B * n*d (walker, unit direction) items in one launch: diag[dir * B + b] = dD[b, dir], out (nullable)
+// the denoiser; bad: device [B * n*d] ints, zeroed by the caller, one per item
+int wide64_jvp_multi(pita_egnn_wide* net, const float* h, const float* x, const float* beta, float* out, float* diag,
+                     int* bad, long long B, hipStream_t stream);
 void wide64_release(pita_egnn_wide* net);
 }  // namespace pita

@@ -374,8 +374,9 @@ struct WideJvpParams {
   float* dout;           // nullable [B, n*dim]
   float* dot_out;        // nullable: dot_out[b * dot_stride + dot_off] = <x_b, dD_b>
   long long dot_stride, dot_off;
-  float* diag_acc;       // nullable: diag_acc[b] += dD[b, dir]
-  const int* only_bad;   // nullable [B]: process only the walkers the matrix-pipe kernel flagged (egnn_wide_mfma_jvp_kernel.hip)
+  float* diag_acc;       // nullable: diag_acc[b] += dD[b, dir]; MULTI: [n*dim, B], diag_acc[dir * B + b] = dD[b, dir]
+  const int* only_bad;   // nullable [B] (MULTI: [B * n*dim], one per item): process only what the matrix-pipe kernel
+                         // flagged (egnn_wide_mfma_jvp_kernel.hip)
 };
 
 namespace {
@@ -444,7 +445,10 @@ __device__ __forceinline__ void dense_mem2(const float* __restrict__ wt, float* 
 #endif
 }
 
-template <int HK>
+// MULTI: the work items are (walker, unit direction) pairs, item = walker * n*dim + direction, each computed exactly as
+// the single-direction launch with vx = vh = null computes it; the item's diagonal entry goes to its own slot (plain
+// store), the item of direction 0 writes the denoiser row; vx, vh, dir, dout and dot_out are ignored.
+template <int HK, bool MULTI = false>
 __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
   const WideParams& p = q.base;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -464,11 +468,16 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
   float* dposn = dpos0 + n * 4;
   float* bc = dposn + n * 4;             // [2][64] broadcast slots (primal, tangent) of the dense layers
   const long long nw = (long long)gridDim.x * waves;
-  for (long long w = (long long)blockIdx.x * waves + wave; w < p.B; w += nw) {
-    if (q.only_bad && q.only_bad[w] == 0) continue;  // wave-uniform
+  const int ndir = n * DIM;
+  const long long items = MULTI ? p.B * ndir : p.B;
+  for (long long item = (long long)blockIdx.x * waves + wave; item < items; item += nw) {
+    if (q.only_bad && q.only_bad[item] == 0) continue;  // wave-uniform
+    const long long w = MULTI ? item / ndir : item;
+    const int dir = MULTI ? (int)(item - w * ndir) : q.dir;
+    const float* const vxp = MULTI ? nullptr : q.vx;
     const float hval = p.t[w];
     const float bet = p.has_beta ? p.beta[w] : 0.f;
-    const float vh = q.vh ? q.vh[w] : 0.f;
+    const float vh = (!MULTI && q.vh) ? q.vh[w] : 0.f;
     // score_net.py:26-29 and their h-derivatives
     const float c_s = 1.0f / (1.0f + hval), c_in = 1.0f / sqrtf(1.0f + hval), sh = sqrtf(hval);
     const float c_out = sh * c_in, tfeat = 0.125f * logf(hval);
@@ -477,7 +486,7 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
     for (int qd = lane; qd < n * DIM; qd += 64) {
       const int i = qd / DIM, k = qd - i * DIM;
       const float xv = p.x[w * n * DIM + qd];
-      const float dx = q.vx ? q.vx[w * n * DIM + qd] : (qd == q.dir ? 1.0f : 0.0f);
+      const float dx = vxp ? vxp[w * n * DIM + qd] : (qd == dir ? 1.0f : 0.0f);
       const float v = c_in * xv, dv = fmaf(c_in, dx, (vh * dc_in) * xv);
       pos[i * 4 + k] = v; pos0[i * 4 + k] = v;
       dpos[i * 4 + k] = dv; dpos0[i * 4 + k] = dv;
@@ -598,23 +607,40 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
       const float F = (pos[i * 4 + k] - pos0[i * 4 + k]) - mean[k];
       const float dF = (dpos[i * 4 + k] - dpos0[i * 4 + k]) - dmean[k];
       const float xc = p.x[w * n * DIM + qd];
-      const float dx = q.vx ? q.vx[w * n * DIM + qd] : (qd == q.dir ? 1.0f : 0.0f);
+      const float dx = vxp ? vxp[w * n * DIM + qd] : (qd == dir ? 1.0f : 0.0f);
       const float dD = fmaf(c_s, dx, fmaf(c_out, dF, vh * fmaf(dc_s, xc, dc_out * F)));
-      if (p.out) p.out[w * n * DIM + qd] = fmaf(c_s, xc, c_out * F);
-      if (q.dout) q.dout[w * n * DIM + qd] = dD;
+      if (p.out && (!MULTI || dir == 0)) p.out[w * n * DIM + qd] = fmaf(c_s, xc, c_out * F);
+      if (!MULTI && q.dout) q.dout[w * n * DIM + qd] = dD;
       dot = fmaf(xc, dD, dot);
-      if (qd == q.dir) diag = dD;
+      if (qd == dir) diag = dD;
     }
-    if (q.dot_out) {
-      const float s = wwave_sum(dot);
-      if (lane == 0) q.dot_out[w * q.dot_stride + q.dot_off] = s;
-    }
-    if (q.diag_acc && q.dir >= 0) {
+    if (MULTI) {
       const float s = wwave_sum(diag);
-      if (lane == 0) q.diag_acc[w] += s;
+      if (lane == 0) q.diag_acc[(long long)dir * p.B + w] = s;
+    } else {
+      if (q.dot_out) {
+        const float s = wwave_sum(dot);
+        if (lane == 0) q.dot_out[w * q.dot_stride + q.dot_off] = s;
+      }
+      if (q.diag_acc && q.dir >= 0) {
+        const float s = wwave_sum(diag);
+        if (lane == 0) q.diag_acc[w] += s;
+      }
     }
     wfence();
   }
+}
+
+// trace[b] = sum over the n*dim directions, in direction order, of diag[dir * B + b]: from +0 and in fp32 these are the
+// adds, in the order, of n*dim single-direction launches accumulating into a zeroed diag_acc (the build contracts
+// nothing), so the sum has their bits.  One thread per walker; the [n*dim, B] layout makes every read coalesced.
+__global__ void __launch_bounds__(256) egnn_wide_trace_reduce_kernel(const float* __restrict__ diag, float* __restrict__ trace,
+                                                                     long long B, int ndir) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.0f;
+  for (int k = 0; k < ndir; ++k) s += diag[(long long)k * B + b];
+  trace[b] = s;
 }
 
 }  // namespace
@@ -1027,6 +1053,7 @@ extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
   PitaDeviceGuard guard(net->device);
   wide64_release(net);
   (void)hipFree(net->d_vjp_ws);
+  (void)hipFree(net->d_jdiag);
   (void)hipFree(net->d_w);
   (void)hipFree(net->d_estatic);
   delete net;
@@ -1129,6 +1156,46 @@ extern "C" int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const f
                            150 * 1024, 2, B, g);
   if (rc != PITA_OK) return rc;
   return wide_launch("pita_egnn_wide_jvp", p.H <= 32 ? egnn_wide_jvp_kernel<32> : egnn_wide_jvp_kernel<64>, g, q, st);
+}
+
+// trace(J_x D) over all n*d unit directions and, optionally, D in ONE call: the launches of pita_egnn_wide_jvp(dir = k,
+// diag_acc) for k = 0 .. n*d - 1 as one launch over (walker, direction) items -- same kernels, same arithmetic per item,
+// same repair contract per item -- and a reduction that adds the diagonal entries in direction order: bit-identical
+extern "C" int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta,
+                                             float* trace, float* denoiser_out, int64_t B, void* stream) {
+  PITA_REQUIRE(net && B >= 0, "pita_egnn_wide_jacobian_trace: bad argument");
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(h && x && trace, "pita_egnn_wide_jacobian_trace: null argument");
+  PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_jacobian_trace: beta required (condition_beta)");
+  PitaDeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  WideJvpParams q{};
+  WideParams& p = q.base;
+  p = wide_params(net, B, 1);
+  p.x = x; p.t = h; p.beta = beta; p.out = denoiser_out;
+  const int ndir = p.n * p.dim;
+  const long long items = (long long)B * ndir;
+  PITA_HIP_CHECK(grow_scratch(net->d_jdiag, net->jdiag_bytes, sizeof(float) * (size_t)items, st));
+  q.dir = -1; q.diag_acc = net->d_jdiag;
+  if (pita_egnn_wide_uses_matrix_pipe(net)) {
+    const size_t need = sizeof(int) * (size_t)items;
+    PITA_HIP_CHECK(grow_scratch(net->d_jbad, net->jbad_bytes, need, st));
+    PITA_HIP_CHECK(hipMemsetAsync(net->d_jbad, 0, need, st));
+    const int r64 = wide64_jvp_multi(net, h, x, beta, denoiser_out, net->d_jdiag, net->d_jbad, B, st);
+    if (r64 == PITA_OK) q.only_bad = net->d_jbad;
+    else if (r64 != 1) return r64;
+  }
+  WideGrid g;
+  int rc = wide_grid("pita_egnn_wide_jacobian_trace", net,
+                     sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + 2 * WIDE_HP), 150 * 1024, 2, items, g);
+  if (rc != PITA_OK) return rc;
+  rc = wide_launch("pita_egnn_wide_jacobian_trace", p.H <= 32 ? egnn_wide_jvp_kernel<32, true> : egnn_wide_jvp_kernel<64, true>,
+                   g, q, st);
+  if (rc != PITA_OK) return rc;
+  hipLaunchKernelGGL(egnn_wide_trace_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, net->d_jdiag, trace,
+                     (long long)B, ndir);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
 }
 
 // Fused sampler on the wide backbone: n_steps Euler-Maruyama steps of the NOT-debiased reverse VE-SDE in one launch

@@ -35,8 +35,8 @@ struct Wide64JvpParams {
   float* dout;       // nullable: dD
   float* dot_out;    // nullable: dot_out[b * dot_stride + dot_off] = <x_b, dD_b>
   long long dot_stride, dot_off;
-  float* diag_acc;   // nullable: diag_acc[b] += dD[b, dir]
-  int* bad;          // [B], zeroed by the launch wrapper: 1 = walker left to the vector-pipe kernel
+  float* diag_acc;   // nullable: diag_acc[b] += dD[b, dir]; MULTI: [N*DIM, B], diag_acc[dir * B + b] = dD[b, dir]
+  int* bad;          // [B] (MULTI: [B * N*DIM], one per item), zeroed by the launch wrapper: 1 = left to the vector-pipe kernel
 };
 
 template <int N, int DIM, int WAVES>
@@ -86,7 +86,11 @@ __device__ __forceinline__ void silu16_d(f32x16& m, f32x16& g) {
   }
 }
 
-template <int N, int DIM, int WAVES, bool ATT, bool TANH>
+// MULTI: the work items are (walker, unit direction) pairs, item = walker * N*DIM + direction (adjacent items share a
+// walker's inputs), each computed exactly as the single-direction launch with vx = vh = null computes it; the item's
+// diagonal entry dD[dir] goes to its own slot (plain store), the item of direction 0 writes the denoiser row; vx, vh, dir,
+// dout and dot_out are ignored.
+template <int N, int DIM, int WAVES, bool ATT, bool TANH, bool MULTI = false>
 __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64JvpParams p) {
   using C = Wide64JvpCfg<N, DIM, WAVES>;
   static_assert(C::NT == 1, "one walker per wave, one column tile");
@@ -112,10 +116,15 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
   const bool valid = cl < N;
   const int live = valid ? 1 : 0;
 
-  for (long long w = (long long)blockIdx.x * WAVES + wave; w < p.B; w += (long long)gridDim.x * WAVES) {
+  constexpr int NDIR = N * DIM;
+  const long long items = MULTI ? p.B * NDIR : p.B;
+  for (long long item = (long long)blockIdx.x * WAVES + wave; item < items; item += (long long)gridDim.x * WAVES) {
+    const long long w = MULTI ? item / NDIR : item;
+    const int dir = MULTI ? (int)(item - w * NDIR) : p.dir;
+    const float* const vxp = MULTI ? nullptr : p.vx;
     const float hv = p.h[w];
     const float bet = p.has_beta ? p.beta[w] : 0.f;
-    const float vh = p.vh ? p.vh[w] : 0.f;
+    const float vh = (!MULTI && p.vh) ? p.vh[w] : 0.f;
     // score_net.py:26-29 and their h-derivatives
     const float c_s = 1.0f / (1.0f + hv), c_in = 1.0f / sqrtf(1.0f + hv), sh = sqrtf(hv);
     const float c_out = sh * c_in, tfeat = 0.125f * logf(hv);
@@ -126,7 +135,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
     for (int k = 0; k < DIM; ++k) {
       const long long e = (w * N + col) * DIM + k;
       xin[k] = valid ? p.x[e] : 0.f;
-      dxin[k] = valid ? (p.vx ? p.vx[e] : ((col * DIM + k) == p.dir ? 1.0f : 0.0f)) : 0.f;
+      dxin[k] = valid ? (vxp ? vxp[e] : ((col * DIM + k) == dir ? 1.0f : 0.0f)) : 0.f;
       const float ps = c_in * xin[k], dps = fmaf(c_in, dxin[k], (vh * dc_in) * xin[k]);
       if (hh == 0) {
         pos0[col * DIM + k] = ps; posbuf0[col * DIM + k] = ps;
@@ -325,16 +334,21 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
     float dot = 0.f, nbad = 0.f;
     for (int q = 0; q < N; ++q) { dot += red[q * 2]; nbad += red[q * 2 + 1]; }
     if (nbad != 0.f) {  // wave-uniform: the walker is one wave's
-      if (lane == 0) p.bad[w] = 1;
+      if (lane == 0) p.bad[item] = 1;
     } else if (valid && hh == 0) {
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
         const long long e = (w * N + col) * DIM + k;
-        if (p.out) p.out[e] = Dv[k];
-        if (p.dout) p.dout[e] = dD[k];
-        if (p.diag_acc && !p.vx && (col * DIM + k) == p.dir) p.diag_acc[w] += dD[k];
+        if (MULTI) {
+          if (p.out && dir == 0) p.out[e] = Dv[k];
+          if ((col * DIM + k) == dir) p.diag_acc[(long long)dir * p.B + w] = dD[k];
+        } else {
+          if (p.out) p.out[e] = Dv[k];
+          if (p.dout) p.dout[e] = dD[k];
+          if (p.diag_acc && !p.vx && (col * DIM + k) == p.dir) p.diag_acc[w] += dD[k];
+        }
       }
-      if (p.dot_out && col == 0) p.dot_out[w * p.dot_stride + p.dot_off] = dot;
+      if (!MULTI && p.dot_out && col == 0) p.dot_out[w * p.dot_stride + p.dot_off] = dot;
     }
     wave_lds_fence();
   }
@@ -343,6 +357,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
 struct Wide64JvpShape {
   int n, dim, waves;
   void (*kernel[2][2])(Wide64JvpParams);  // [attention][tanh]
+  void (*multi[2][2])(Wide64JvpParams);   // the same over (walker, direction) items
   size_t (*lds_bytes)(int);
 };
 template <int N, int DIM, int WAVES>
@@ -351,20 +366,26 @@ static size_t wide64_jvp_lds_of(int L) { return Wide64JvpCfg<N, DIM, WAVES>::lds
   Wide64JvpShape { N, DIM, WAVES,                                                                                          \
                    {{egnn_wide64_jvp_kernel<N, DIM, WAVES, false, false>, egnn_wide64_jvp_kernel<N, DIM, WAVES, false, true>}, \
                     {egnn_wide64_jvp_kernel<N, DIM, WAVES, true, false>, egnn_wide64_jvp_kernel<N, DIM, WAVES, true, true>}},  \
+                   {{egnn_wide64_jvp_kernel<N, DIM, WAVES, false, false, true>,                                            \
+                     egnn_wide64_jvp_kernel<N, DIM, WAVES, false, true, true>},                                             \
+                    {egnn_wide64_jvp_kernel<N, DIM, WAVES, true, false, true>,                                             \
+                     egnn_wide64_jvp_kernel<N, DIM, WAVES, true, true, true>}},                                             \
                    wide64_jvp_lds_of<N, DIM, WAVES> }
 // alanine dipeptide (22 atoms); other particle counts take the vector-pipe kernel
 static const Wide64JvpShape kWide64JvpShapes[] = {PITA_WIDE64_JVP_SHAPE(22, 3, 4)};
 
-// returns PITA_OK when the matrix-pipe kernel took the launch, 1 when the particle system has no instantiation
-int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* vx, int dir,
-               const float* vh, float* out, float* dout, float* dot_out, long long dot_stride, long long dot_off,
-               float* diag_acc, int* bad, long long B, hipStream_t stream) {
+// returns PITA_OK when the matrix-pipe kernel took the launch, 1 when the particle system has no instantiation;
+// multi: all n*d unit directions of every walker in one launch (vx, dir, vh, dout, dot_out unused; diag_acc: [n*d, B])
+static int wide64_jvp_launch(pita_egnn_wide* net, bool multi, const float* h, const float* x, const float* beta,
+                             const float* vx, int dir, const float* vh, float* out, float* dout, float* dot_out,
+                             long long dot_stride, long long dot_off, float* diag_acc, int* bad, long long B,
+                             hipStream_t stream) {
   if (!net->shape64) return 1;
   const Wide64JvpShape* s = nullptr;
   for (const auto& t : kWide64JvpShapes)
     if (t.n == net->cfg.n_particles && t.dim == net->cfg.n_dim) s = &t;
   if (!s || s->lds_bytes(net->cfg.n_layers) > 160 * 1024) return 1;
-  auto kernel = s->kernel[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
+  auto kernel = (multi ? s->multi : s->kernel)[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
   const size_t lds = s->lds_bytes(net->cfg.n_layers);
   PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
   Wide64JvpParams p{};
@@ -374,11 +395,24 @@ int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float*
   p.B = B; p.x = x; p.h = h; p.beta = beta; p.vx = vx; p.vh = vh; p.dir = vx ? -1 : dir;
   p.out = out; p.dout = dout; p.dot_out = dot_out; p.dot_stride = dot_stride; p.dot_off = dot_off; p.diag_acc = diag_acc;
   p.bad = bad;
-  const long long want = (B + s->waves - 1) / s->waves, cap = net->n_cu;  // one 4-wave block per CU
+  const long long items = multi ? B * s->n * s->dim : B;  // one item per wave
+  const long long want = (items + s->waves - 1) / s->waves, cap = net->n_cu;  // one 4-wave block per CU
   const unsigned grid = (unsigned)(want < cap ? want : cap);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->waves * 64), lds, stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
+}
+
+int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* vx, int dir,
+               const float* vh, float* out, float* dout, float* dot_out, long long dot_stride, long long dot_off,
+               float* diag_acc, int* bad, long long B, hipStream_t stream) {
+  return wide64_jvp_launch(net, false, h, x, beta, vx, dir, vh, out, dout, dot_out, dot_stride, dot_off, diag_acc, bad, B,
+                           stream);
+}
+
+int wide64_jvp_multi(pita_egnn_wide* net, const float* h, const float* x, const float* beta, float* out, float* diag,
+                     int* bad, long long B, hipStream_t stream) {
+  return wide64_jvp_launch(net, true, h, x, beta, nullptr, -1, nullptr, out, nullptr, nullptr, 0, 0, diag, bad, B, stream);
 }
 
 }  // namespace pita

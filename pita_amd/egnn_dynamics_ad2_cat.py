@@ -178,6 +178,26 @@ class EGNN_dynamics_AD2_cat(nn.Module):
                                                  _lib.stream_ptr(x_t.device)), "pita_egnn_wide_jvp")
         return out, dout
 
+    def jacobian_trace(self, h_t, x_t, beta, want_denoiser=False):
+        """(trace, D or None): trace(J_x D_theta(h, x)) per walker, exactly, over all n*d unit directions, and with
+        ``want_denoiser`` D_theta(h, x) -- ONE call (pita_egnn_wide_jacobian_trace: one launch over (walker, direction)
+        pairs and a reduction) with the bits of the n*d ``jvp(direction=k, diag_acc=trace)`` launches it replaces.
+        ``VEReverseSDE._score_divergence_terms`` takes it for the exact divergence of the score (utils.py:30-51)."""
+        x_t = _lib.dev_tensor(x_t, "x_t")
+        B = x_t.shape[0]
+        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
+        b = None
+        if self.condition_beta:
+            if beta is None:
+                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
+            b = _as_batch(beta, B, x_t.device)
+        trace = torch.empty(B, device=x_t.device)
+        den = torch.empty_like(x_t) if want_denoiser else None
+        _lib.check(_lib.lib().pita_egnn_wide_jacobian_trace(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(),
+                                                            _lib.ptr(b), trace.data_ptr(), _lib.ptr(den), B,
+                                                            _lib.stream_ptr(x_t.device)), "pita_egnn_wide_jacobian_trace")
+        return trace, den
+
     def vjp(self, h_t, x_t, beta, cot=None, want_primal=True, want_dot_h=False):
         """(D, J_x D^T cot[, <cot, dD/dh>]): the EDM denoiser around this backbone and its reverse-mode derivative for a
         per-walker cotangent (default: x_t itself) from ONE launch (pita_egnn_wide_vjp) -- same contract as

@@ -1,0 +1,66 @@
+"""Timing of trace(J_x D) on the wide EGNN backbone (EGNN_dynamics_AD2_cat, 22 atoms, hidden 64 x 5 layers, attention + tanh,
+condition_beta): the n*d = 66 single-direction launches exactly as VEReverseSDE._denoiser_jacobian_terms issues them against
+the single call EGNN_dynamics_AD2_cat.jacobian_trace (pita_egnn_wide_jacobian_trace), alternating, in one process on one
+device, device-event timing.
+python tools/time_wide_trace.py [--batches 512,2048,4096] [--reps 20] [--warmup 3] [--commit HASH]
+Prints per batch size the median and min-max of both in ms, whether the two traces agree bit for bit, and the difference
+against the loop's own min-max spread.  --commit: recorded in the header (default: git rev-parse of the tree it runs in)."""
+import argparse, os, statistics, subprocess, sys
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import pita_amd as pa
+from pita_amd.egnn_dynamics_ad2_cat import EGNN_dynamics_AD2_cat
+ap = argparse.ArgumentParser()
+ap.add_argument("--batches", default="512,2048,4096")
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--commit", default=None)
+a = ap.parse_args()
+assert torch.cuda.is_available(), "needs the GPU: a timing taken anywhere else says nothing"
+commit = a.commit
+if commit is None:
+    r = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True)
+    commit = r.stdout.strip() if r.returncode == 0 else "unknown"
+print(f"tools/time_wide_trace.py  commit {commit}  device {torch.cuda.get_device_name(0)}  torch {torch.__version__}")
+print(f"EGNN_dynamics_AD2_cat(22, 3, hidden_nf=64, n_layers=5, attention, tanh, condition_beta), seeded weights; "
+      f"{a.warmup} warm-up + {a.reps} timed repetitions per path, alternating, device events")
+torch.manual_seed(7)
+net = EGNN_dynamics_AD2_cat(22, 3, hidden_nf=64, n_layers=5, tanh=True, attention=True, condition_beta=True)
+sde = pa.VEReverseSDE(noise_schedule=None, score_net=None, debias_inference=True)
+assert net.uses_matrix_pipe("cuda:0")
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); out = fn(); e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+for B in (int(b) for b in a.batches.split(",")):
+    gen = torch.Generator().manual_seed(B)
+    x = torch.randn(B, 22, 3, generator=gen)
+    x = (x - x.mean(1, keepdim=True)).reshape(B, 66).cuda()
+    h = (torch.rand(B, generator=gen) * 2.0 + 0.05).cuda()
+    beta = (torch.rand(B, generator=gen) + 0.5).cuda()
+    loop = lambda: sde._denoiser_jacobian_terms(net, h, x, beta, False)  # (D, trace, jtx, None): 66 launches
+    single = lambda: net.jacobian_trace(h, x, beta, want_denoiser=True)  # (trace, D): one call
+    for _ in range(a.warmup):
+        loop(); single()
+    torch.cuda.synchronize()
+    t = {"loop": [], "single": []}
+    for _ in range(a.reps):
+        ms, (D_l, tr_l, _, _) = timed(loop)
+        t["loop"].append(ms)
+        ms, (tr_s, D_s) = timed(single)
+        t["single"].append(ms)
+    same = torch.equal(tr_l, tr_s) and torch.equal(D_l, D_s)
+    s = lambda v: f"median {statistics.median(v):8.3f} (min {min(v):8.3f}, max {max(v):8.3f})"
+    gain = statistics.median(t["loop"]) - statistics.median(t["single"])
+    spread = max(t["loop"]) - min(t["loop"])
+    verdict = "beyond the loop's spread" if gain > spread else ("within the loop's spread" if gain >= -spread
+                                                                else "SINGLE CALL SLOWER beyond the loop's spread")
+    print(f"B={B}: 66-launch loop {s(t['loop'])} ms | single call {s(t['single'])} ms | loop - single {gain:8.3f} ms "
+          f"(x{statistics.median(t['loop']) / statistics.median(t['single']):.2f}), loop spread {spread:.3f} ms: {verdict} | "
+          f"bits {'identical' if same else 'DIFFER'}", flush=True)
