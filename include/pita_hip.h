@@ -93,19 +93,19 @@ int pita_dw_descent(float* x, const float* noise, int64_t B, int n_particles, in
                     uint64_t walker_offset, int64_t step0, int remove_mean, void* stream);
 
 /* Fused MALA chain on a pair target: all nsteps of metropolis_hastings_mala / _adaptive
- * (pita/src/models/components/sde_integration.py:28-45,362-470) in one launch, walkers resident on chip; bit-identical to
- * pita_*_logp_force + pita_mala_propose + pita_*_logp_force + pita_mala_accept + pita_mala_adapt step after step.
+ * (pita/src/models/components/sde_integration.py:28-45,362-470) in fused launches, walkers resident on chip; bit-identical
+ * to pita_*_logp_force + pita_mala_propose + pita_*_logp_force + pita_mala_accept + pita_mala_adapt step after step.
  * pita_lj_mala: LJ13 and LJ55; pita_dw_mala: DW4.  x [B, n*d] and logp [B] (log-density of x on entry) are updated in
  * place; dt_dev holds the step size (adapted in place when adaptive != 0, against the acceptance rate over `total` walkers
  * -- this rank's B: with several ranks the global rate needs the launch-per-kernel path); rates_out [nsteps] receives the
  * acceptance rates.  noise [nsteps, B, n*d] / uniforms [nsteps, B] nullable -> Philox keyed (seed, walker key, step0 + s,
  * particle / 0xFFFFF), walker key = walker_ids[w] or walker_offset + w.  workspace: 8-byte aligned device scratch of
  * pita_lj_mala_workspace_bytes(nsteps) bytes.
- * The adaptive chain synchronises the grid once per step (the global acceptance count decides the next step size); the
- * grid is sized to the co-resident capacity of an idle device; batches beyond it make one HBM round trip of the walkers
- * per step (steps outside, tiles inside) instead of staying on chip.  If the device was NOT idle and a
- * block's bounded wait runs out, the chain is invalid: dt_dev[0] and every rates_out[s] are set to NaN (x / logp hold
- * garbage) and the caller must rerun from its own copy of the walkers -- pita_amd.WeightedSDEIntegrator does. */
+ * A non-adaptive chain is ONE launch with the walkers resident on chip over all steps.  An adaptive chain is one launch
+ * per step: the order of the stream is what lets a step see the acceptance count of the step before, and every launch
+ * derives its step size on the device from dt_dev[0] and the counts so far (no host synchronisation).  There is no
+ * grid-wide barrier and no wait inside the kernels, so these entry points cannot time out: they have no NaN result and
+ * no rerun protocol, and the device need not be idle. */
 size_t pita_lj_mala_workspace_bytes(int nsteps);
 int pita_lj_mala(float* x, float* logp, const float* noise /*nullable*/, const float* uniforms /*nullable*/, int64_t B,
                  int n_particles, int n_dim, float temperature, float energy_factor, float dist_eps, float eps, float rm,
@@ -248,7 +248,7 @@ int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise /*nullable*/, in
  * per step: the order of the stream is what lets a step see the acceptance count of the step before, and every launch
  * derives its step size on the device from dt_dev[0] and the counts so far (no host synchronisation).  There is no
  * grid-wide barrier and no wait inside the kernel, so this entry point cannot time out: it has no NaN result and no
- * rerun protocol, unlike pita_lj_mala / pita_dw_mala.  The chain runs in the launch plan of pita_ff_descent, so a handle
+ * rerun protocol.  The chain runs in the launch plan of pita_ff_descent, so a handle
  * that exists is taken; PITA_EUNSUPPORTED is reserved for a handle whose plan cannot hold the chain.
  * ff, dt_dev, workspace non-null, B >= 0, n_steps >= 0, total > 0 and the workspace alignment are checked before any
  * device call (PITA_EINVAL); B == 0 or n_steps == 0 is PITA_OK and leaves dt_dev as it is. */

@@ -698,17 +698,18 @@ __global__ void __launch_bounds__(256, 2) lj13_descent_kernel(float* __restrict_
 
 
 // ---------------------------------------------------------------------------- fused MALA chain on the LJ13 target
-// All post_mcmc_steps of metropolis_hastings_mala(_adaptive) (sde_integration.py:362-470) in ONE launch with the walkers
-// resident in LDS: per step  force(x) -> proposal x' = (x + dt/2 F) + sqrt(dt) xi (:28-45) -> logp, force at x' ->
+// The post_mcmc_steps of metropolis_hastings_mala(_adaptive) (sde_integration.py:362-470) in fused launches with the
+// walkers resident in LDS: per step  force(x) -> proposal x' = (x + dt/2 F) + sqrt(dt) xi (:28-45) -> logp, force at x' ->
 // log q_f, log q_b, accept iff log u < (logp' - logp) + (log q_b - log q_f) -> the reference's float blend of x and
 // logp, optional centring, acceptance count -> step-size adaptation dt *= 1.1 / dt /= 1.1 on the GLOBAL acceptance rate
 // (:439-443).  The two target evaluations per step are the two halves of lj13_kernel<2> (half 1 hands its partial forces
 // and energy over through LDS), the elementwise arithmetic and its summation orders are those of mala_propose_kernel /
 // mala_accept_kernel / mala_adapt_kernel (sampler_kernels.hip): the chain is bit-identical to the launch-per-kernel
-// path.  The adaptive variant needs every block's acceptance count before the next step: one grid-wide barrier per step
-// (all blocks co-resident: checked by the launch wrapper).  Only the counter itself crosses blocks, so the barrier is ONE
-// relaxed agent-scope atomic add of (1 << 32 | accepted) per block and a relaxed polling load -- no release / acquire
-// fences, which at agent scope write back and invalidate the XCD's L2 (measured: ~80 us per step with them); bounded spin.
+// path.  A launch runs steps [step_base, step_base + steps) of the chain, tiles outside, steps inside.  No grid-wide
+// barrier and no wait of any kind: the only cross-block traffic is one integer atomic add of a tile's accepted walkers
+// per step.  A non-adaptive chain is ONE launch; an adaptive chain, whose step size needs every tile's count of the step
+// before, is one launch per step (stream order is the barrier), each deriving its step size from dt_dev[0] and the
+// counts so far (mala_replay_dt).
 
 template <bool UNIT_RM>
 __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x, float* __restrict__ logp, long long B,
@@ -719,15 +720,10 @@ __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x
   __shared__ __attribute__((aligned(16))) float fb[WPB * D];   // half 1's partial forces
   __shared__ float es1[WPB];
   __shared__ int cnt[4];
-  __shared__ int total_acc;
   const int tid = threadIdx.x;
   const int half = tid / WPB, wl = tid - half * WPB;
-  const long long nblk = (B + WPB - 1) / WPB;
-  // Tiles of 128 walkers.  Non-adaptive chains and adaptive chains with at most one tile per block keep a tile in LDS
-  // for all steps; an adaptive chain with more tiles than resident blocks runs steps outside, tiles inside, one HBM
-  // round trip of the walkers per step (the grid barrier of a step needs every tile's count first).
-  const bool roundtrip = q.adaptive && nblk > (long long)gridDim.x;
-  double dt = q.dt_dev[0];
+  const long long nblk = (B + WPB - 1) / WPB;  // tiles of 128 walkers; a tile stays in LDS for all steps of the launch
+  const double dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
   long long w0 = 0, wg = 0;
   int nw = 0, nfl = 0, row = 0;
   bool act = false;
@@ -861,62 +857,20 @@ __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x
       __syncthreads();
     return cnt[0] + cnt[1] + cnt[2] + cnt[3];
   };
-  // a step's count of this block goes to the grid; adaptive chains wait for everybody's and adapt dt
-  auto publish = [&](int s, int c) {
-    if (tid == 0) {
-      __hip_atomic_fetch_add(&q.sync[s], (1ull << 32) | (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (q.adaptive) {  // grid-wide barrier: wait until every block has added its count
-        const unsigned long long v = mala_grid_wait(q.sync, s, q.nsteps,
-                                                    (unsigned long long)gridDim.x + q.debug_missing_blocks, q.spin_limit);
-        total_acc = (int)(v & 0xFFFFFFFFull);
-      }
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    load(blk);
+    for (int st = 0; st < q.steps; ++st) {
+      const int s = q.step_base + st, c = step(s);
+      if (tid == 0 && c) __hip_atomic_fetch_add(&q.sync[s], (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();
-    if (q.adaptive) {
-      const float rate = (float)total_acc / (float)q.total;
-      dt = ((double)rate > 0.55) ? dt * 1.1 : dt / 1.1;  // sde_integration.py:439-443
-    }
-  };
-  if (roundtrip) {
-    for (int s = 0; s < q.nsteps; ++s) {
-      int c = 0;
-      for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        load(blk);
-        c += step(s);
-        store();
-      }
-      publish(s, c);
-    }
-  } else {
-    for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-      load(blk);
-      for (int s = 0; s < q.nsteps; ++s) publish(s, step(s));
-      store();
-    }
+    store();
   }
 }
 
-// acceptance rates of all steps and the final step size from the per-step counts (same arithmetic as mala_adapt_kernel).
-// A chain that raised its error flag (a grid-barrier spin ran out: the blocks were not all co-resident after all, e.g.
-// because another stream or process held compute units) adapted dt from different counts in different blocks: its
-// walkers are not a valid chain.  dt and every rate are then NaN, which no caller can mistake for a result
-// (WeightedSDEIntegrator._mala restores its backup and reruns the launch-per-kernel chain).
+// acceptance rates of all steps and the final step size from the per-step counts: the replay over the whole chain
 __global__ void mala_finish_kernel(double* dt_dev, const unsigned long long* sync, int nsteps, long long total, int adaptive,
                                    float* rates_out) {
-  const bool failed = sync[nsteps] != 0;
-  double dt = dt_dev[0];
-  for (int s = 0; s < nsteps; ++s) {
-    const float rate = (float)(int)(sync[s] & 0xFFFFFFFFull) / (float)total;
-    if (rates_out) rates_out[s] = failed ? __builtin_nanf("") : rate;
-    if (adaptive) dt = ((double)rate > 0.55) ? dt * 1.1 : dt / 1.1;
-  }
-  dt_dev[0] = failed ? __builtin_nan("") : dt;
-}
-
-int mala_spin_limit() {
-  const char* e = getenv("PITA_DEBUG_MALA_SPIN_LIMIT");
-  if (e && *e) return atoi(e);
-  return 1 << 22;
+  dt_dev[0] = mala_replay_dt(dt_dev, sync, nsteps, total, adaptive, rates_out);
 }
 
 int launch_mala_finish(double* dt_dev, const unsigned long long* sync, int nsteps, long long total, int adaptive,
@@ -1190,21 +1144,24 @@ extern "C" int pita_dw_descent(float* x, const float* noise, int64_t B, int n, i
                               descent_params(nsteps, dt, noise_scale, sqrt_dt, seed, walker_offset, step0, remove_mean), stream);
 }
 
+// one counter per step (and one spare slot that callers have always sized their buffers with)
 extern "C" size_t pita_lj_mala_workspace_bytes(int nsteps) { return 8 * (size_t)((nsteps > 0 ? nsteps : 0) + 1); }
 
-// shared tail of the fused-chain entry points: zero the per-step counters, run the chain, derive rates and final dt
-template <class Chain>
+// shared frame of the fused-chain entry points: zero the per-step counters, run the chain, derive rates and final dt.
+// A non-adaptive chain is one launch; an adaptive chain is one launch per step, and the order of the stream is what lets
+// a step see the counts of the steps before it.
+template <class Launch>
 static int run_mala_chain(int nsteps, double* dt_dev, int adaptive, int64_t total, float* rates_out, void* workspace,
-                          MalaParams& q, void* stream, Chain&& chain) {
+                          MalaParams& q, void* stream, Launch&& launch) {
   PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "fused MALA: workspace must be 8-byte aligned");
   unsigned long long* sync = static_cast<unsigned long long*>(workspace);
   PITA_HIP_CHECK(hipMemsetAsync(sync, 0, pita_lj_mala_workspace_bytes(nsteps), (hipStream_t)stream));
   q.sync = sync;
-  q.spin_limit = mala_spin_limit();
-  const char* miss = getenv("PITA_DEBUG_MALA_MISSING_BLOCKS");
-  q.debug_missing_blocks = (miss && *miss) ? atoi(miss) : 0;
-  const int rc = chain();
-  if (rc != PITA_OK) return rc;
+  q.steps = adaptive ? 1 : nsteps;
+  for (q.step_base = 0; q.step_base < nsteps; q.step_base += q.steps) {
+    const int rc = launch();
+    if (rc != PITA_OK) return rc;
+  }
   return launch_mala_finish(dt_dev, sync, nsteps, (long long)total, adaptive, rates_out, stream);
 }
 
@@ -1226,7 +1183,7 @@ extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const flo
   hipStream_t s = (hipStream_t)stream;
   MalaParams q{};
   q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids; q.seed = seed;
-  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev; q.nsteps = nsteps;
+  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev;
   q.adaptive = adaptive; q.remove_mean = remove_mean;
   if (n == 55) {
     return run_mala_chain(nsteps, dt_dev, adaptive, total, rates_out, workspace, q, stream, [&]() {
@@ -1237,7 +1194,8 @@ extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const flo
   }
   const long long nblk = (B + 127) / 128;
   const bool unit = p.rm2 == 1.0f;
-  static PerDevice<int> capacity_on;  // co-resident blocks of the chain kernel, per device
+  // one residency of the chain kernel, per device: a performance choice (no tail wave), nothing depends on co-residency
+  static PerDevice<int> capacity_on;
   int& capacity = capacity_on.get();
   if (capacity == 0) {
     int per_cu = 0, dev = 0;
@@ -1272,7 +1230,7 @@ extern "C" int pita_dw_mala(float* x, float* logp, const float* noise, const flo
   p.inv_T = 1.0f / temperature; p.a = a; p.b = b; p.c = c; p.d0 = d0;
   MalaParams q{};
   q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids; q.seed = seed;
-  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev; q.nsteps = nsteps;
+  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev;
   q.adaptive = adaptive; q.remove_mean = remove_mean;
   return run_mala_chain(nsteps, dt_dev, adaptive, total, rates_out, workspace, q, stream, [&]() {
     if (B == 0) return (int)PITA_OK;

@@ -395,8 +395,8 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
 // No grid-wide barrier and no wait of any kind: the only cross-block traffic is one integer atomicAdd of the accepted
 // walkers per tile and step.  A non-adaptive chain is ONE launch (tiles outside, steps inside); an adaptive chain is one
 // launch per step (stream order is the barrier), each deriving its step size from dt_dev[0] and the counts of the
-// steps before it -- the replay loop of mala_finish_kernel (energy_kernels.hip), which runs last and leaves the rates
-// and the final step size.
+// steps before it (mala_replay_dt, pair_common.h); mala_finish_kernel (energy_kernels.hip) runs last and leaves the
+// rates and the final step size.
 struct FfMalaParams {
   float* x;                  // [B][3 n] walkers, updated in place
   float* logp;               // [B] log-density of x, carried
@@ -406,7 +406,7 @@ struct FfMalaParams {
   unsigned long long seed, walker_offset;
   long long step0, total, B;
   const double* dt_dev;      // step size on entry of the CHAIN (not written by this kernel)
-  unsigned long long* sync;  // [n_steps + 1] accepted walkers per step (low 32 bits, the layout launch_mala_finish reads)
+  unsigned long long* sync;  // [n_steps + 1] accepted walkers per step (the layout launch_mala_finish reads)
   int step_base, steps;      // this launch runs steps [step_base, step_base + steps) of the chain
   int adaptive, remove_mean;
 };
@@ -419,13 +419,8 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaP
   float *qf = L.gs, *qb = qf + WPB * n, *flag = qb + WPB * n;  // [WPB][n] partial |x' - fwd mean|^2, |x - bwd mean|^2; [WPB] 1.0 = accepted
   const int tid = threadIdx.x, wl = tid / n, a = tid - wl * n;
   const bool lane_on = wl < WPB;
-  // step size of step `step_base`: constant, or adapted on the acceptance rates of the steps before (mala_adapt_kernel's rule)
-  double dtd = q.dt_dev[0];
-  if (q.adaptive)
-    for (int s = 0; s < q.step_base; ++s) {
-      const float rate = (float)(int)(q.sync[s] & 0xFFFFFFFFull) / (float)q.total;
-      dtd = ((double)rate > 0.55) ? dtd * 1.1 : dtd / 1.1;  // sde_integration.py:439-443
-    }
+  // step size of step `step_base`: constant, or adapted on the acceptance rates of the steps before
+  const double dtd = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
   const float hdt = (float)(0.5 * dtd), sdt = (float)sqrt(dtd), tdt = (float)(2.0 * dtd);
   const float sc = -p.inv_kT * p.length_scale;  // d logp / d x_model
   const long long nblk = (q.B + WPB - 1) / WPB;

@@ -28,40 +28,30 @@ struct MalaParams {
   unsigned long long seed, walker_offset;
   long long step0, total;
   const double* dt_dev;
-  int nsteps, adaptive, remove_mean;
-  int spin_limit;            // bound of the adaptive chain's grid-barrier spin (polls); see mala_spin_limit()
-  int debug_missing_blocks;  // tests only (PITA_DEBUG_MALA_MISSING_BLOCKS): the barrier waits for this many blocks that never come
-  unsigned long long* sync;  // [nsteps + 1]: per step (blocks arrived << 32 | walkers accepted), error flag; zeroed by the wrapper
+  int step_base, steps;      // this launch runs steps [step_base, step_base + steps) of the chain (adaptive: steps == 1)
+  int adaptive, remove_mean;
+  unsigned long long* sync;  // [chain steps] walkers accepted per step, added with an integer atomic; zeroed by the wrapper
 };
 
-// Polls a block may spend in the per-step grid barrier of an adaptive chain before it raises the error flag
-// sync[nsteps] (the launch then poisons dt / rates with NaN and the caller reruns the launch-per-kernel chain).
-// PITA_DEBUG_MALA_SPIN_LIMIT overrides it (tests force the timeout path with 0).
-int mala_spin_limit();
-
 #ifdef __HIPCC__
-// One block's bounded wait for the `nblocks` arrivals of step s (sync[s] = arrivals << 32 | accepted walkers); returns the
-// counter as last read.  A wait that runs out raises the chain's error flag sync[nsteps].  The flag is read before the
-// first poll and every 64 polls, so once ANY block has given up every other wait of the launch ends at once: a chain
-// whose grid turned out not to be co-resident costs one timeout, not one per remaining step and block.
-__device__ __forceinline__ unsigned long long mala_grid_wait(unsigned long long* sync, int s, int nsteps,
-                                                             unsigned long long nblocks, int spin_limit) {
-  unsigned long long v = 0;
-  int spins = 0;
-  while (((v = __hip_atomic_load(&sync[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) < nblocks) {
-    if ((spins & 63) == 0 && __hip_atomic_load(&sync[nsteps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-    if (++spins > spin_limit) {  // never hang the device
-      __hip_atomic_store(&sync[nsteps], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
+// Step size of chain step `step_base` of a fused chain: dt_dev[0] as the chain found it and, when adaptive,
+// mala_adapt_kernel's rule (sampler_kernels.hip; sde_integration.py:439-443) replayed over the accepted counts
+// sync[0 .. step_base) of the steps before, which earlier launches of the stream left.  rates_out, when given, receives
+// the acceptance rates of those steps.
+__device__ __forceinline__ double mala_replay_dt(const double* dt_dev, const unsigned long long* sync, int step_base,
+                                                 long long total, int adaptive, float* rates_out = nullptr) {
+  double dt = dt_dev[0];
+  if (adaptive || rates_out)
+    for (int s = 0; s < step_base; ++s) {
+      const float rate = (float)(int)sync[s] / (float)total;
+      if (rates_out) rates_out[s] = rate;
+      if (adaptive) dt = ((double)rate > 0.55) ? dt * 1.1 : dt / 1.1;
     }
-    __builtin_amdgcn_s_sleep(2);
-  }
-  return v;
+  return dt;
 }
 #endif
 
-// rates_out[s] and the final dt from the per-step counts of a fused chain; NaN everywhere when the chain flagged a
-// barrier timeout (energy_kernels.hip)
+// rates_out[s] and the final dt from the per-step counts of a fused chain (energy_kernels.hip)
 int launch_mala_finish(double* dt_dev, const unsigned long long* sync, int nsteps, long long total, int adaptive,
                        float* rates_out, void* stream);
 

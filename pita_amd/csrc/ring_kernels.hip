@@ -361,16 +361,12 @@ __global__ void __launch_bounds__(256) ring_descent_kernel(float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------- fused MALA chain
-// All post_mcmc_steps of metropolis_hastings_mala(_adaptive) (sde_integration.py:362-470) in one launch; arithmetic and
-// summation orders of ring_energy_kernel + mala_propose_kernel + ring_energy_kernel + mala_accept_kernel +
-// mala_adapt_kernel: bit-identical to the launch-per-kernel chain.
-//   * non-adaptive, or adaptive with at most one walker group per wave: a wave keeps its walkers on chip for all steps;
-//   * adaptive with more groups than resident waves (LJ55 at 32 768 walkers per GPU): steps outside, groups inside,
-//     the walkers make one HBM round trip per step (1.3 KB per LJ55 walker against ~2 x 1 500 pairs of arithmetic).
-// The adaptive step size needs the global acceptance count of a step before the next one: one grid-wide barrier per
-// step made of ONE relaxed agent-scope atomic add of (1 << 32 | accepted) per block and a relaxed polling load (see
-// lj13_mala_kernel); the grid never exceeds the co-resident capacity (launch wrapper); a spin that runs out raises
-// sync[nsteps] and the finish kernel poisons dt and the rates with NaN.
+// The post_mcmc_steps of metropolis_hastings_mala(_adaptive) (sde_integration.py:362-470) in fused launches; arithmetic
+// and summation orders of ring_energy_kernel + mala_propose_kernel + ring_energy_kernel + mala_accept_kernel +
+// mala_adapt_kernel: bit-identical to the launch-per-kernel chain.  A launch runs steps [step_base, step_base + steps) of
+// the chain, groups outside, steps inside: a wave keeps its walkers on chip for all steps of the launch.  As in
+// lj13_mala_kernel there is no grid-wide barrier and no wait: a non-adaptive chain is one launch, an adaptive chain one
+// launch per step, each deriving its step size from dt_dev[0] and the counts of the steps before it (mala_replay_dt).
 template <int N, int DIM, int KIND, bool UNIT_RM>
 __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, float* __restrict__ logp, long long B,
                                                         PairParams p, MalaParams q) {
@@ -379,13 +375,12 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
   // the DPP-row mapping (13 particles on 16 lanes) is validated for the energy kernel only
   static_assert(R::STRIDE == 4 || R::STRIDE == 64, "descent / MALA chains: quad or whole-wave walkers only");
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  __shared__ int cnt[4];
-  __shared__ int total_acc;
-  // non-adaptive chains only count: per block and step in LDS, flushed once at the end (a global atomic per wave and
-  // step -- 32 768 x nsteps adds on nsteps addresses for LJ55 -- serialises in the L2 and costs more than the chain)
+  // accepted walkers per block and step in LDS, flushed once at the end (a global atomic per wave and step -- 32 768 x
+  // nsteps adds on nsteps addresses for LJ55 -- serialises in the L2 and costs more than the chain)
   constexpr int STEP_CNT = 512;
   __shared__ int stepcnt[STEP_CNT];
-  for (int t = threadIdx.x; t < STEP_CNT; t += 256) stepcnt[t] = 0;
+  const int cnt_end = q.step_base + q.steps < STEP_CNT ? q.step_base + q.steps : STEP_CNT;  // chain steps counted in LDS
+  for (int t = q.step_base + threadIdx.x; t < cnt_end; t += 256) stepcnt[t] = 0;
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float* tab1 = sm + wave * 2 * R::TAB_F;  // current walkers; pad slot of an entry: this particle's |x' - fwd mean|^2
@@ -393,8 +388,7 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
   const R r(lane);
   const long long ngroups = (B + R::WPW - 1) / R::WPW, nwaves = (long long)gridDim.x * 4;
   const long long g0 = (long long)blockIdx.x * 4 + wave;
-  const bool roundtrip = q.adaptive && ngroups > nwaves;  // steps outside, groups inside
-  double dt = q.dt_dev[0];
+  const double dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
   float xi[DIM], lp = 0.f;
 
   // one MALA step of the walker group in (xi, lp, tab1); returns the number of accepted walkers of this wave
@@ -485,22 +479,6 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
     return __popcll(__ballot(act && r.i == 0 && af != 0.f));
   };
 
-  // grid-wide exchange of a step's acceptance count (adaptive chains)
-  auto exchange = [&](int s, int acc_wave) {
-    if (lane == 0) cnt[wave] = acc_wave;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned long long c = (unsigned long long)(cnt[0] + cnt[1] + cnt[2] + cnt[3]);
-      __hip_atomic_fetch_add(&q.sync[s], (1ull << 32) | c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long v = mala_grid_wait(q.sync, s, q.nsteps, (unsigned long long)gridDim.x + q.debug_missing_blocks,
-                                                  q.spin_limit);
-      total_acc = (int)(v & 0xFFFFFFFFull);
-    }
-    __syncthreads();
-    const float rate = (float)total_acc / (float)q.total;
-    dt = ((double)rate > 0.55) ? dt * 1.1 : dt / 1.1;  // sde_integration.py:439-443
-  };
-
   auto load = [&](long long ws) {
     load_x<N, DIM>(r, x, ws, xi);
     lp = logp[ws];
@@ -516,46 +494,24 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
     }
   };
 
-  if (roundtrip) {
-    for (int s = 0; s < q.nsteps; ++s) {
-      int acc_wave = 0;
-      for (long long g = g0; g < ngroups; g += nwaves) {
-        const long long w = g * R::WPW + r.wl;
-        const bool act = r.real && w < B;
-        const long long ws = w < B ? w : B - 1;
-        load(ws);
-        acc_wave += step(ws, act, s);
-        store(w, act);
+  for (long long g = g0; g < ngroups; g += nwaves) {
+    const long long w = g * R::WPW + r.wl;
+    const bool act = r.real && w < B;
+    const long long ws = w < B ? w : B - 1;
+    load(ws);
+    for (int st = 0; st < q.steps; ++st) {
+      const int s = q.step_base + st, acc = step(ws, act, s);
+      if (lane == 0 && acc) {
+        if (s < STEP_CNT) atomicAdd(&stepcnt[s], acc);
+        else __hip_atomic_fetch_add(&q.sync[s], (unsigned long long)acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      exchange(s, acc_wave);  // (a walker is re-read by the wave that wrote it: no fence needed across the barrier)
     }
-  } else {
-    // q.adaptive here means: one group per wave at most, every wave takes part in every step's barrier
-    const long long gmax = q.adaptive ? g0 + 1 : ngroups;
-    for (long long g = g0; g < gmax; g += nwaves) {
-      const bool have = g < ngroups;
-      const long long w = (have ? g : 0) * R::WPW + r.wl;
-      const bool act = have && r.real && w < B;
-      const long long ws = w < B ? w : B - 1;
-      load(ws);
-      for (int s = 0; s < q.nsteps; ++s) {
-        const int acc = step(ws, act, s);
-        if (q.adaptive) {
-          exchange(s, acc);
-        } else if (lane == 0 && acc) {
-          if (s < STEP_CNT) atomicAdd(&stepcnt[s], acc);
-          else __hip_atomic_fetch_add(&q.sync[s], (unsigned long long)acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      store(w, act);
-    }
-    if (!q.adaptive) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < STEP_CNT && t < q.nsteps; t += 256)
-        if (stepcnt[t])
-          __hip_atomic_fetch_add(&q.sync[t], (unsigned long long)stepcnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    store(w, act);
   }
+  __syncthreads();
+  for (int t = q.step_base + threadIdx.x; t < cnt_end; t += 256)
+    if (stepcnt[t])
+      __hip_atomic_fetch_add(&q.sync[t], (unsigned long long)stepcnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <int N, int DIM, int KIND>
@@ -617,7 +573,9 @@ struct RingLaunch {
   static int mala(float* x, float* logp, long long B, const PairParams& p, const MalaParams& q, hipStream_t s) {
     const size_t lds = sizeof(float) * 4 * 2 * R::TAB_F;
     const bool unit = KIND == E_LJ && p.rm2 == 1.0f;
-    static PerDevice<int> per_cu_on[2];  // co-resident blocks per CU of the chain kernel, per device
+    // resident blocks per CU of the chain kernel, per device: the grid is one residency as a performance choice (no tail
+    // wave); nothing depends on the blocks being co-resident
+    static PerDevice<int> per_cu_on[2];
     int& slot = per_cu_on[unit ? 1 : 0].get();
     if (slot == 0) {
       int v = 0;

@@ -81,10 +81,11 @@ class LennardJonesEnergy(BaseMoleculeEnergy):
 
     def fused_mala(self, x, logp, num_steps, dt_dev, adaptive, total, noise=None, uniforms=None, seed=0, walker_offset=0,
                    walker_ids=None, step0=0, remove_mean=True, rates_out=None):
-        """All ``num_steps`` MALA steps in ONE launch, in place on ``x`` / ``logp`` / ``dt_dev`` (pita_lj_mala;
-        metropolis_hastings_mala(_adaptive), sde_integration.py:362-470).  Returns None when the fused kernel does not
-        apply (other particle numbers, normalised coordinates, an LJ13 adaptive chain too large to be co-resident): the
-        caller then runs the launch-per-kernel path, which gives the same bits.  LJ13 and LJ55 have fused chains."""
+        """All ``num_steps`` MALA steps in fused launches, in place on ``x`` / ``logp`` / ``dt_dev`` (pita_lj_mala;
+        metropolis_hastings_mala(_adaptive), sde_integration.py:362-470): one launch for a non-adaptive chain, one per
+        step for an adaptive one.  Returns None when the fused kernel does not apply (other particle numbers, normalised
+        coordinates): the caller then runs the launch-per-kernel path, which gives the same bits.  LJ13 and LJ55 have
+        fused chains."""
         if self.should_normalize or self.smooth or self.n_particles not in (13, 55) or self.n_spatial_dim != 3:
             return None
         L = _lib.lib()

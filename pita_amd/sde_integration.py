@@ -562,8 +562,7 @@ class WeightedSDEIntegrator:
         """MALA with the reference's finite-mask semantics (:362-470): non-finite-logp walkers are set aside and
         re-appended AFTER the valid ones (order not preserved, quirk Q7).  Proposal, accept/reject and the step-size
         adaptation run as HIP kernels with the step size on the device: no host synchronisation inside the chain (the
-        fused chains synchronise once, after the launch, when the acceptance rates -- which also say whether an adaptive
-        chain's grid barrier held -- are copied to the host).
+        acceptance rates are copied to the host afterwards, and only when the caller asks for them).
         With several ranks the acceptance count is all-reduced so the adaptation sees the global rate, as the
         reference (which runs the chain on the gathered batch on every rank) does."""
         n, d = self._geometry(x, energy_function)
@@ -595,8 +594,9 @@ class WeightedSDEIntegrator:
             # :397-398 centres through maybe_remove_mean, the adaptive variant (:458-461) unconditionally
             rm = int(bool(getattr(energy_function, "is_molecule", False)) and (adaptive or bool(self.should_mean_free)))
             st = _lib.stream_ptr(dev)
-            # pair targets with a fused chain kernel: every step in ONE launch, walkers LDS-resident (bit-identical
-            # to the loop below); the global acceptance rate of several ranks needs the per-step all-reduce below
+            # targets with a fused chain kernel: walkers on chip, one launch for a non-adaptive chain, one per step for
+            # an adaptive one (bit-identical to the loop below); the global acceptance rate of several ranks needs the
+            # per-step all-reduce below
             if fused and world == 1 and Bv > 0 and hasattr(energy_function, "fused_mala"):
                 nz = uu = None
                 if noise is not None:
@@ -607,25 +607,11 @@ class WeightedSDEIntegrator:
                     uu = torch.stack([_lib.dev_tensor(uniforms[i], "uniforms").reshape(-1) for i in range(steps)]).contiguous()
                     if tuple(uu.shape) != (steps, Bv):
                         raise ValueError(f"MALA uniforms have shape {tuple(uu.shape)}, expected {(steps, Bv)}")
-                # an adaptive chain synchronises the grid every step and assumes an idle device; if a block's bounded wait
-                # runs out (another stream or process held compute units) the launch marks the chain invalid with NaN
-                # rates: restore the walkers and run the launch-per-kernel chain, which cannot fail this way
-                backup = (x_valid.clone(), logp.clone(), dt_dev.clone()) if adaptive else None
                 if energy_function.fused_mala(x_valid, logp, steps, dt_dev, adaptive, total, noise=nz, uniforms=uu, seed=key,
                                               walker_offset=walker_offset, walker_ids=ids, step0=0, remove_mean=rm,
                                               rates_out=rates) is not None:
-                    # the validity check is the chain's ONE host synchronisation: the transfer of the rates the caller
-                    # asked for (or of the final step size when it did not)
-                    host_rates = rates[:steps].tolist() if return_acceptance_rate else (dt_dev.tolist() if adaptive else [])
-                    if adaptive and any(math.isnan(r) for r in host_rates):
-                        x_valid.copy_(backup[0])
-                        logp.copy_(backup[1])
-                        dt_dev.copy_(backup[2])
-                        rates.zero_()
-                        self._fused_mala_fallbacks = getattr(self, "_fused_mala_fallbacks", 0) + 1
-                    else:
-                        out = torch.cat([x_valid, x_invalid], dim=0)
-                        return (out, host_rates) if return_acceptance_rate else (out, None)
+                    out = torch.cat([x_valid, x_invalid], dim=0)
+                    return (out, rates[:steps].tolist()) if return_acceptance_rate else (out, None)
             for i in range(steps):
                 if Bv > 0:
                     _, grad = energy_function(x_valid, return_force=True)

@@ -1292,10 +1292,10 @@ def test_post_processing_golden(pa, golden, n):
 @pytest.mark.parametrize("adaptive", [False, True])
 @pytest.mark.parametrize("B,steps", [(777, 6), (128, 3), (5, 4), (65536, 5), (70001, 3)])
 def test_fused_mala_equals_per_step(pa, golden, B, steps, adaptive):
-    """pita_lj_mala (all steps, both target evaluations per step, accept / reject and step-size adaptation in one launch)
-    == the launch-per-kernel chain, bit for bit: walkers, acceptance rates, with Philox and with injected noise /
-    uniforms, with and without centring, ragged and full blocks, with a walker that is set aside (quirk Q7), and with more
-    tiles than co-resident blocks (70 001 walkers: the adaptive chain then makes one HBM round trip per step)."""
+    """pita_lj_mala (all steps, both target evaluations per step, accept / reject and step-size adaptation in fused
+    launches) == the launch-per-kernel chain, bit for bit: walkers, acceptance rates, with Philox and with injected noise
+    / uniforms, with and without centring, ragged and full blocks, with a walker that is set aside (quirk Q7), and with
+    more tiles than blocks in the grid (70 001 walkers: a block then takes several tiles per launch)."""
     g = golden("post_lj13.npz")
     e = pa.LennardJonesEnergy(39, 13, 3)
     gen = torch.Generator().manual_seed(B + steps)
@@ -1362,8 +1362,8 @@ def _ring_target(pa, name, B, gen):
 def test_fused_ring_mala_equals_per_step(pa, name, B, steps, dt, adaptive):
     """pita_lj_mala (LJ55) / pita_dw_mala (DW4): the ring-kernel chains == the launch-per-kernel chain, bit for bit --
     walkers, acceptance rates; Philox and injected noise / uniforms; with and without centring; ragged wave groups; a
-    batch beyond the co-resident capacity (LJ55 10 007 walkers = 10 007 wave groups > 8 192 resident waves; DW4 700 001
-    walkers), where the adaptive chain makes one HBM round trip per step and the non-adaptive one loops over groups."""
+    batch beyond one residency of the grid (LJ55 10 007 walkers = 10 007 wave groups > 8 192 resident waves; DW4 700 001
+    walkers), where a wave takes several groups per launch."""
     gen = torch.Generator().manual_seed(B + steps)
     e, n, d, x0 = _ring_target(pa, name, B, gen)
     D = n * d
@@ -1421,80 +1421,79 @@ def test_fused_ring_mala_equals_per_step(pa, name, B, steps, dt, adaptive):
         assert same.float().mean() > 0.99, float(same.float().mean())
 
 
+def _mala_target(pa, golden, name, B, gen):
+    """(target, n, d, MALA step size, B near-equilibrium walkers) of the three targets with a fused pair-target chain."""
+    if name != "lj13":
+        e, n, d, x0 = _ring_target(pa, name, B, gen)
+        return e, n, d, (2e-4 if name == "lj55" else 0.05), x0
+    base = T(golden("post_lj13.npz")["x0"])
+    x0 = O.remove_mean(base[torch.arange(B) % base.shape[0]] + 0.02 * torch.randn(B, 39, generator=gen), 13, 3).cuda()
+    return pa.LennardJonesEnergy(39, 13, 3), 13, 3, 3e-4, x0
+
+
 @pytest.mark.parametrize("name", ["lj13", "lj55", "dw4"])
-def test_fused_adaptive_mala_barrier_timeout_falls_back(pa, golden, name, monkeypatch):
-    """The adaptive chain's per-step grid barrier assumes an idle device.  PITA_DEBUG_MALA_SPIN_LIMIT=0 makes every block
-    that is not the last to arrive give up at once: the launch must report the chain invalid (NaN rates and step size
-    through the C ABI) and WeightedSDEIntegrator must restore the walkers and produce the launch-per-kernel result."""
-    gen = torch.Generator().manual_seed(5)
-    steps = 4
-    if name == "lj13":
-        g = golden("post_lj13.npz")
-        e, n, d, dt = pa.LennardJonesEnergy(39, 13, 3), 13, 3, 3e-4
-        base = T(g["x0"])
-        x0 = O.remove_mean(base[torch.arange(2000) % base.shape[0]] + 0.02 * torch.randn(2000, 39, generator=gen), 13, 3).cuda()
-    else:
-        e, n, d, x0 = _ring_target(pa, name, 2000, gen)
-        dt = 2e-4 if name == "lj55" else 0.05
+def test_fused_adaptive_mala_barrier_timeout_falls_back(pa, golden, name):
+    """The adaptive fused chain on a device that is NOT idle (the condition its former per-step grid barrier could not
+    tolerate): while a second stream holds tens of milliseconds of matmuls, the chain on the current stream -- through
+    the integrator and through the C ABI -- still equals the launch-per-kernel chain computed on the idle device, bit
+    for bit, with finite rates and step size, and the integrator has no rerun protocol left to count."""
+    steps, (e, n, d, dt, x0) = 4, _mala_target(pa, golden, name, 2000, torch.Generator().manual_seed(5))
     mk = lambda: pa.WeightedSDEIntegrator(sde=None, num_integration_steps=1, start_resampling_step=0, end_resampling_step=1,
                                           post_mcmc_steps=steps, dt_negative_time=dt, adaptive_mcmc=True, seed=3)
     want = mk().metropolis_hastings_mala_adaptive(x0.clone(), e, dt_init=dt, return_acceptance_rate=True, fused=False)
-    monkeypatch.setenv("PITA_DEBUG_MALA_SPIN_LIMIT", "0")
-    # through the C ABI: the invalid chain is reported, not returned as a result
-    lp = e(x0)
-    xc = x0.clone()
+    lp, xc, rates = e(x0), x0.clone(), torch.zeros(steps, device="cuda")
     dt_dev = torch.tensor([dt], device="cuda", dtype=torch.float64)
-    rates = torch.zeros(steps, device="cuda")
-    assert e.fused_mala(xc, lp, steps, dt_dev, True, x0.shape[0], seed=1, rates_out=rates) is not None
-    assert torch.isnan(rates).all() and torch.isnan(dt_dev).all()
-    integ = mk()
+    a, side, integ = torch.randn(8192, 8192, device="cuda"), torch.cuda.Stream(), mk()
+    a @ a  # (the library's first-call set-up is not part of the queued work)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for _ in range(6):
+            a @ a
     got = integ.metropolis_hastings_mala_adaptive(x0.clone(), e, dt_init=dt, return_acceptance_rate=True)
-    assert integ._fused_mala_fallbacks == 1
-    assert torch.equal(got[0], want[0]) and got[1] == want[1]
-    monkeypatch.delenv("PITA_DEBUG_MALA_SPIN_LIMIT")
-    integ = mk()
-    got = integ.metropolis_hastings_mala_adaptive(x0.clone(), e, dt_init=dt, return_acceptance_rate=True)
-    assert getattr(integ, "_fused_mala_fallbacks", 0) == 0 and torch.equal(got[0], want[0]) and got[1] == want[1]
+    assert e.fused_mala(xc, lp, steps, dt_dev, True, x0.shape[0], seed=mk()._key(2), remove_mean=e.is_molecule,
+                        rates_out=rates) is not None
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want[0]) and got[1] == want[1] and not any("fallback" in k for k in vars(integ))
+    assert torch.equal(xc, want[0]) and rates.tolist() == want[1] and torch.isfinite(rates).all() and torch.isfinite(dt_dev).all()
 
 
-@pytest.mark.parametrize("name", ["lj13", "lj55", "dw4"])
-def test_fused_adaptive_mala_failed_barrier_costs_one_timeout(pa, golden, name, monkeypatch):
-    """A chain whose grid is not fully co-resident (here: PITA_DEBUG_MALA_MISSING_BLOCKS=1 makes every barrier wait for
-    a block that never arrives) must give up ONCE: the block whose bounded spin runs out raises the error flag and
-    every other wait of the launch -- same step, later steps -- ends as soon as it sees the flag.  40 steps with a
-    spin budget of 200 000 polls per wait: one timeout's worth of device time, not 40, and NaN rates."""
-    gen = torch.Generator().manual_seed(6)
-    steps = 40
-    if name == "lj13":
-        g = golden("post_lj13.npz")
-        e, dt = pa.LennardJonesEnergy(39, 13, 3), 3e-4
-        base = T(g["x0"])
-        x0 = O.remove_mean(base[torch.arange(2000) % base.shape[0]] + 0.02 * torch.randn(2000, 39, generator=gen), 13, 3).cuda()
-    else:
-        e, n, d, x0 = _ring_target(pa, name, 2000, gen)
-        dt = 2e-4 if name == "lj55" else 0.05
-    lp = e(x0)
+@pytest.mark.parametrize("name,B", [("lj13", 300), ("lj55", 37), ("dw4", 300)])
+def test_fused_adaptive_mala_final_step_size(pa, golden, name, B):
+    """The step size an adaptive fused chain leaves in dt_dev == the float64 replay of the adaptation rule over the rates
+    it returns (the same IEEE operations) == the dt_dev the launch-per-kernel loop (pita_mala_adapt) leaves, bit for bit."""
+    steps, key, (e, n, d, dt, x0) = 6, 7, _mala_target(pa, golden, name, B, torch.Generator().manual_seed(B))
+    new = lambda: (x0.clone(), e(x0), torch.tensor([dt], device="cuda", dtype=torch.float64), torch.zeros(steps, device="cuda"))
+    x, lp, dt_dev, rates = new()
+    assert e.fused_mala(x, lp, steps, dt_dev, True, B, seed=key, rates_out=rates) is not None
+    replay = dt
+    for r in rates.tolist():  # mala_adapt_kernel's rule in float64
+        replay = replay * 1.1 if r > 0.55 else replay / 1.1
+    assert dt_dev.item() == replay
+    L, st, check = pa._lib.lib(), pa._lib.stream_ptr(x0.device), pa._lib.check
+    (xk, lpk, dtk, rk), xp, count = new(), torch.empty_like(x), torch.zeros(1, device="cuda", dtype=torch.int32)
+    for i in range(steps):
+        _, F = e(xk, return_force=True)
+        check(L.pita_mala_propose(xk.data_ptr(), F.data_ptr(), xp.data_ptr(), 0, B, n, d, dtk.data_ptr(), key, 0, 0, i, st))
+        lpp, Fp = e(xp, return_force=True)
+        check(L.pita_mala_accept(xk.data_ptr(), lpk.data_ptr(), F.data_ptr(), xp.data_ptr(), lpp.data_ptr(), Fp.data_ptr(), 0,
+                                 B, n, d, dtk.data_ptr(), key, 0, 0, i, 1, count.data_ptr(), st))
+        check(L.pita_mala_adapt(dtk.data_ptr(), count.data_ptr(), B, 1, rk[i:].data_ptr(), st))
+    assert torch.equal(dtk, dt_dev) and torch.equal(rk, rates) and torch.equal(xk, x) and torch.equal(lpk, lp)
 
-    def timed(nsteps):
-        xc, lpc = x0.clone(), lp.clone()
-        dt_dev = torch.tensor([dt], device="cuda", dtype=torch.float64)
-        rates = torch.zeros(nsteps, device="cuda")
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0.record()
-        assert e.fused_mala(xc, lpc, nsteps, dt_dev, True, x0.shape[0], seed=1, rates_out=rates) is not None
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1), rates, dt_dev
 
-    monkeypatch.setenv("PITA_DEBUG_MALA_MISSING_BLOCKS", "1")
-    monkeypatch.setenv("PITA_DEBUG_MALA_SPIN_LIMIT", "200000")
-    timed(1)
-    one, r1, _ = timed(1)
-    many, r40, d40 = timed(steps)
-    assert torch.isnan(r1).all() and torch.isnan(r40).all() and torch.isnan(d40).all()
-    print(f"[barrier bail-out/{name}] 1 step {one:.2f} ms, {steps} steps {many:.2f} ms")
-    assert many < 3 * one + 5.0, (one, many)
+@pytest.mark.parametrize("adaptive", [False, True])
+def test_fused_ring_mala_step_index_past_the_lds_counters(pa, adaptive):
+    """520 steps of DW4 on ragged quad groups: the smallest chain whose step index passes the ring kernel's 512 per-block
+    LDS counters (later steps are counted in global memory); walkers and all 520 rates equal the launch-per-kernel chain."""
+    steps, outs = 520, []
+    e, n, d, x0 = _ring_target(pa, "dw4", 37, torch.Generator().manual_seed(steps))
+    for fused in (True, False):
+        integ = pa.WeightedSDEIntegrator(sde=None, num_integration_steps=1, start_resampling_step=0, end_resampling_step=1,
+                                         post_mcmc_steps=steps, dt_negative_time=0.05, adaptive_mcmc=adaptive, seed=9)
+        fn = integ.metropolis_hastings_mala_adaptive if adaptive else integ.metropolis_hastings_mala
+        outs.append(fn(x0.clone(), e, return_acceptance_rate=True, fused=fused, **(dict(dt_init=0.05) if adaptive else {})))
+    assert torch.equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1] and len(outs[0][1]) == steps
+    assert max(outs[0][1][512:]) > 0.0, "the steps past the LDS counters must count too"
 
 
 def test_mala_sets_non_finite_walkers_aside(pa, golden):
