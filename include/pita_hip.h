@@ -143,6 +143,11 @@ int pita_egnn_wide_create(pita_egnn_wide_t** out, const pita_egnn_wide_config* c
 int pita_egnn_wide_destroy(pita_egnn_wide_t* net);
 /* 1 when pita_egnn_wide_eval runs this handle on the matrix-pipe kernel, 0 when on the vector-pipe kernel alone */
 int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net);
+/* 1 when pita_egnn_wide_jvp / pita_egnn_wide_jacobian_trace run this handle's forward-mode launches on the matrix-pipe
+ * kernel (csrc/egnn_wide_mfma_jvp_kernel.hip: instantiated for 22, 33, 42 particles x 3, LDS need within a workgroup's
+ * 160 KB, PITA_WIDE_NO_MFMA unset), 0 when on the vector-pipe kernel alone (13, 55 particles and every shape
+ * pita_egnn_wide_uses_matrix_pipe is 0 for) */
+int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net);
 /* what = 0: vel[B, n*d] = backbone(t[B], x[B, n*d], beta[B]) (mean-free); 1: denoiser D_theta(h = t, x); 2: score */
 int pita_egnn_wide_eval(pita_egnn_wide_t* net, int what, const float* t, const float* x, const float* beta /*nullable*/,
                         float* out, int64_t B, void* stream);
@@ -162,7 +167,10 @@ int pita_egnn_wide_sampler_run(pita_egnn_wide_t* net, float* x, int64_t B, const
  * (nullable), dot_out[b * dot_stride + dot_off] = <x_b, dD_b>, diag_acc[b] += dD[b, dir].  What the debiased
  * Feynman-Kac regime (pita/src/models/components/sdes.py:151-239 with utils.py:30-51, energy_net.py:51-62) needs of
  * EGNN_dynamics_AD2_cat: trace J_x D, J_x D^T x and <x, dD/dh> are sums over such directions; the reference takes them
- * from vmap(jacrev) and autograd.  fp32 vector-pipe kernel (csrc/egnn_wide_kernel.hip: egnn_wide_jvp_kernel). */
+ * from vmap(jacrev) and autograd.  Matrix-pipe kernel (csrc/egnn_wide_mfma_jvp_kernel.hip) for 22, 33 and 42 particles
+ * (pita_egnn_wide_jvp_uses_matrix_pipe), then the fp32 vector-pipe kernel (csrc/egnn_wide_kernel.hip:
+ * egnn_wide_jvp_kernel) on exactly the walkers whose primal or tangent left the f16 range; the vector-pipe kernel alone
+ * for every other shape. */
 int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta /*nullable*/,
                        const float* vx /*nullable*/, int dir, const float* vh /*nullable*/, float* out /*nullable*/,
                        float* dout /*nullable*/, float* dot_out /*nullable*/, int64_t dot_stride, int64_t dot_off,
@@ -179,8 +187,9 @@ int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, co
 
 /* trace(J_x D)(h, x) of the EDM denoiser around the wide backbone and, optionally, D itself: ONE call
  * (replaces n*d pita_egnn_wide_jvp launches, utils.py:30-51); bit-identical to them.  One launch whose work items are
- * (walker, unit direction) pairs -- the matrix-pipe kernel where the particle system has one, the vector-pipe kernel on
- * exactly the items it flagged (and on all items otherwise, or under PITA_WIDE_NO_MFMA) -- writes the diagonal entries
+ * (walker, unit direction) pairs -- the matrix-pipe kernel where pita_egnn_wide_jvp_uses_matrix_pipe (22, 33, 42
+ * particles), the vector-pipe kernel on exactly the items it flagged (and on all items of every other shape, or under
+ * PITA_WIDE_NO_MFMA) -- writes the diagonal entries
  * dD[b, dir] to a handle-owned scratch; a reduction adds them per walker in direction order. */
 int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float* h, const float* x,
                                   const float* beta /*nullable*/, float* trace /*[B]*/,

@@ -37,6 +37,8 @@ int wide64_launch(pita_egnn_wide* net, int what, const float* t, const float* x,
 int wide64_sampler(pita_egnn_wide* net, float* x, long long B, const float* step_tab, int n_steps, const float* noise,
                    unsigned long long seed, unsigned long long walker_offset, long long step0, int remove_mean,
                    double* stats_out, int* bad_from, hipStream_t stream);
+// 1 when the forward-mode kernel on the matrix pipe has an instantiation for the net's particle system whose LDS fits
+int wide64_jvp_available(const pita_egnn_wide* net);
 // forward-mode derivative on the matrix pipe (egnn_wide_mfma_jvp_kernel.hip); returns 1 when the particle system has no
 // instantiation; bad: device [B] ints, zeroed by the caller, set to 1 for walkers left to the vector-pipe kernel
 int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* vx, int dir,

@@ -1048,6 +1048,10 @@ extern "C" int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net) {
   return (net && net->shape64 && getenv("PITA_WIDE_NO_MFMA") == nullptr) ? 1 : 0;
 }
 
+extern "C" int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net) {
+  return (pita_egnn_wide_uses_matrix_pipe(net) && wide64_jvp_available(net)) ? 1 : 0;
+}
+
 extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
   if (!net) return PITA_OK;
   PitaDeviceGuard guard(net->device);
@@ -1122,7 +1126,8 @@ extern "C" int pita_egnn_wide_eval(pita_egnn_wide_t* net, int what, const float*
                      (hipStream_t)stream);
 }
 
-// Forward-mode derivative of the denoiser around the wide backbone (vector-pipe kernel; see egnn_wide_jvp_kernel)
+// Forward-mode derivative of the denoiser around the wide backbone (egnn_wide_jvp_kernel, behind the matrix-pipe kernel
+// where pita_egnn_wide_jvp_uses_matrix_pipe)
 extern "C" int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta, const float* vx,
                                   int dir, const float* vh, float* out, float* dout, float* dot_out, int64_t dot_stride,
                                   int64_t dot_off, float* diag_acc, int64_t B, void* stream) {

@@ -8,7 +8,9 @@
 // D(h, x) = c_s x + c_out F(c_noise(h), c_in(h) x, beta)  (score_net.py:13-43 around egnn_dynamics_ad2_cat.py:157-203).
 //
 // Mapping: egnn_wide64_kernel's one-walker-per-wave instantiation (one column tile: lane = (column, half of the 64 hidden
-// features), dense layers as 2 x 2 blocks of the f16 two-piece MFMA tile) with ONE tangent direction carried beside the
+// features), dense layers as 2 x 2 blocks of the f16 two-piece MFMA tile); particle systems of more than 32 atoms take
+// NT = 2 waves per item, one per 32-column tile, that share the item's LDS tables and meet at a block barrier wherever
+// a table is published (each wave keeps the one-tile register footprint).  ONE tangent direction is carried beside the
 // primal: every linear map is applied to the tangent with the same weight fragments (the tangent of a GEMM is the GEMM of
 // the tangent), every SiLU passes its derivative sigma + y (1 - sigma) / kS on from the primal's own sigmoid (no further
 // transcendental), tangents travel in the scaled units of their primals (egnn_common.h: kS, F16_SX, F16_SW), partner
@@ -45,12 +47,21 @@ struct Wide64JvpCfg {
   static constexpr int NT = NCOLP / 32;
   static constexpr int PB_F = NCOLP * W64_PBS;
   static constexpr int POS_F = NCOLP * DIM;
-  static constexpr int WAVE_F = 2 * PB_F + 6 * POS_F;  // partner table + its tangent, pos[2], pos0 + their tangents
+  static constexpr int IPB = WAVES / NT;               // items per block: NT waves (one per column tile) share an item
+  static constexpr int WAVE_F = 2 * PB_F + 6 * POS_F;  // per item: partner table + its tangent, pos[2], pos0 + their tangents
   static __host__ __device__ constexpr int vec_f(int L) { return ((W64_HEAD_F + L * W64_LAYER_F) + 3) & ~3; }
   static __host__ __device__ constexpr size_t lds_bytes(int L) {
-    return sizeof(float) * (size_t)(vec_f(L) + N * 64 + WAVES * WAVE_F);
+    return sizeof(float) * (size_t)(vec_f(L) + N * 64 + IPB * WAVE_F);
   }
 };
+
+// orders an item's LDS tables between their writers and readers: the item is one wave's (NT == 1) or NT waves' of the
+// block (a block barrier; every wave of the block reaches each one the same number of times)
+template <int NT>
+__device__ __forceinline__ void item_fence() {
+  if constexpr (NT == 1) wave_lds_fence();
+  else __syncthreads();
+}
 
 // SiLU of egnn_common.h's PREC 2 forms with the derivative: in v = kS z (UNSCALE: the accumulator 16 kS z), out
 // y = kS silu(z) in place and g = d silu / dz = s + (y / kS)(1 - s) with s the sigmoid the primal computed anyway
@@ -93,7 +104,8 @@ __device__ __forceinline__ void silu16_d(f32x16& m, f32x16& g) {
 template <int N, int DIM, int WAVES, bool ATT, bool TANH, bool MULTI = false>
 __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64JvpParams p) {
   using C = Wide64JvpCfg<N, DIM, WAVES>;
-  static_assert(C::NT == 1, "one walker per wave, one column tile");
+  static_assert(C::NT * C::IPB == WAVES && C::NT <= 2, "NT waves per item, one per column tile");
+  constexpr int NT = C::NT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int L = p.L;
   const int vec_f = C::vec_f(L);
@@ -103,7 +115,8 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
   __syncthreads();
 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, cl = lane & 31, hh = lane >> 5;
-  float* PB = est + N * 64 + wave * C::WAVE_F;
+  const int slot = wave / NT, tile = wave % NT;  // the item's place in the block, this wave's column tile
+  float* PB = est + N * 64 + slot * C::WAVE_F;
   float* dPB = PB + C::PB_F;
   float* posbuf0 = dPB + C::PB_F;
   float* posbuf1 = posbuf0 + C::POS_F;
@@ -112,13 +125,19 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
   float* dposbuf1 = dposbuf0 + C::POS_F;
   float* dpos0 = dposbuf1 + C::POS_F;
   const f32x16 zero16 = {0};
-  const int col = cl, nodei = cl < N ? cl : 0;
-  const bool valid = cl < N;
+  const int col = tile * 32 + cl, nodei = col < N ? col : 0;
+  const bool valid = col < N;
   const int live = valid ? 1 : 0;
 
   constexpr int NDIR = N * DIM;
   const long long items = MULTI ? p.B * NDIR : p.B;
-  for (long long item = (long long)blockIdx.x * WAVES + wave; item < items; item += (long long)gridDim.x * WAVES) {
+  // block-uniform trip count (the NT == 2 body holds block barriers): a slot past the last item computes that item again
+  // in its own tables and writes nothing (at most one wasted item per block and launch, in the block's last trip); with
+  // one wave per item such a wave has no barrier to keep and leaves
+  for (long long base = (long long)blockIdx.x * C::IPB; base < items; base += (long long)gridDim.x * C::IPB) {
+    const bool active = base + slot < items;
+    if (NT == 1 && !active) break;
+    const long long item = active ? base + slot : items - 1;
     const long long w = MULTI ? item / NDIR : item;
     const int dir = MULTI ? (int)(item - w * NDIR) : p.dir;
     const float* const vxp = MULTI ? nullptr : p.vx;
@@ -153,7 +172,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
         dhfeat[b][r] = wt[r] * dtf;
       }
     }
-    wave_lds_fence();
+    item_fence<NT>();
 
     float* poscur = posbuf0; float* posnext = posbuf1;
     float* dposcur = dposbuf0; float* dposnext = dposbuf1;
@@ -174,7 +193,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
           lds_store16(dPB + col * W64_PBS + b * 32 + hh * 16, dpb[b]);
         }
       }
-      wave_lds_fence();
+      item_fence<NT>();
 
       W64Mat w2f, wc1f;
       w2f.load(ml, WM_W2, lane);
@@ -298,7 +317,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
         hfeat[0] += o[0] * F16_UNSCALE; hfeat[1] += o[1] * F16_UNSCALE;
         dhfeat[0] += d_o[0] * F16_UNSCALE; dhfeat[1] += d_o[1] * F16_UNSCALE;
       }
-      wave_lds_fence();
+      item_fence<NT>();
       float* tmp = poscur; poscur = posnext; posnext = tmp;
       tmp = dposcur; dposcur = dposnext; dposnext = tmp;
     }
@@ -313,7 +332,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
       dF[k] = dposcur[col * DIM + k] - dpos0[col * DIM + k];
       if (hh == 0) { scr[col * DIM + k] = F[k]; dscr[col * DIM + k] = dF[k]; }
     }
-    wave_lds_fence();
+    item_fence<NT>();
     float Dv[DIM], dD[DIM], part = 0.f;
     bool ok = true;
 #pragma unroll
@@ -327,14 +346,15 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
       part = fmaf(xin[k], dD[k], part);
       ok = ok && __builtin_isfinite(Dv[k]) && __builtin_isfinite(dD[k]);
     }
-    wave_lds_fence();
+    item_fence<NT>();
     float* red = scr;       // [NCOLP][2]: <x, dD> of the column, its non-finite flag
     if (hh == 0) { red[col * 2] = valid ? part : 0.f; red[col * 2 + 1] = (valid && !ok) ? 1.0f : 0.0f; }
-    wave_lds_fence();
+    item_fence<NT>();
     float dot = 0.f, nbad = 0.f;
     for (int q = 0; q < N; ++q) { dot += red[q * 2]; nbad += red[q * 2 + 1]; }
-    if (nbad != 0.f) {  // wave-uniform: the walker is one wave's
-      if (lane == 0) p.bad[item] = 1;
+    if (!active) {  // a slot past the last item: its recomputed copy writes nothing
+    } else if (nbad != 0.f) {  // uniform over the item's waves: all read the same flags
+      if (lane == 0 && tile == 0) p.bad[item] = 1;
     } else if (valid && hh == 0) {
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
@@ -350,7 +370,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
       }
       if (!MULTI && p.dot_out && col == 0) p.dot_out[w * p.dot_stride + p.dot_off] = dot;
     }
-    wave_lds_fence();
+    item_fence<NT>();
   }
 }
 
@@ -371,8 +391,19 @@ static size_t wide64_jvp_lds_of(int L) { return Wide64JvpCfg<N, DIM, WAVES>::lds
                     {egnn_wide64_jvp_kernel<N, DIM, WAVES, true, false, true>,                                             \
                      egnn_wide64_jvp_kernel<N, DIM, WAVES, true, true, true>}},                                             \
                    wide64_jvp_lds_of<N, DIM, WAVES> }
-// alanine dipeptide (22 atoms); other particle counts take the vector-pipe kernel
-static const Wide64JvpShape kWide64JvpShapes[] = {PITA_WIDE64_JVP_SHAPE(22, 3, 4)};
+// alanine dipeptide (22 atoms: one wave per item), tri-alanine (33) and ACE-(ALA)3-NME (42: two waves per item, one per
+// column tile); other particle counts take the vector-pipe kernel
+static const Wide64JvpShape kWide64JvpShapes[] = {PITA_WIDE64_JVP_SHAPE(22, 3, 4), PITA_WIDE64_JVP_SHAPE(33, 3, 4),
+                                                  PITA_WIDE64_JVP_SHAPE(42, 3, 4)};
+
+static const Wide64JvpShape* wide64_jvp_shape(const pita_egnn_wide* net) {
+  if (!net->shape64) return nullptr;
+  for (const auto& t : kWide64JvpShapes)
+    if (t.n == net->cfg.n_particles && t.dim == net->cfg.n_dim && t.lds_bytes(net->cfg.n_layers) <= 160 * 1024) return &t;
+  return nullptr;
+}
+
+int wide64_jvp_available(const pita_egnn_wide* net) { return wide64_jvp_shape(net) ? 1 : 0; }
 
 // returns PITA_OK when the matrix-pipe kernel took the launch, 1 when the particle system has no instantiation;
 // multi: all n*d unit directions of every walker in one launch (vx, dir, vh, dout, dot_out unused; diag_acc: [n*d, B])
@@ -380,11 +411,8 @@ static int wide64_jvp_launch(pita_egnn_wide* net, bool multi, const float* h, co
                              const float* vx, int dir, const float* vh, float* out, float* dout, float* dot_out,
                              long long dot_stride, long long dot_off, float* diag_acc, int* bad, long long B,
                              hipStream_t stream) {
-  if (!net->shape64) return 1;
-  const Wide64JvpShape* s = nullptr;
-  for (const auto& t : kWide64JvpShapes)
-    if (t.n == net->cfg.n_particles && t.dim == net->cfg.n_dim) s = &t;
-  if (!s || s->lds_bytes(net->cfg.n_layers) > 160 * 1024) return 1;
+  const Wide64JvpShape* s = wide64_jvp_shape(net);
+  if (!s) return 1;
   auto kernel = (multi ? s->multi : s->kernel)[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
   const size_t lds = s->lds_bytes(net->cfg.n_layers);
   PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
@@ -395,8 +423,9 @@ static int wide64_jvp_launch(pita_egnn_wide* net, bool multi, const float* h, co
   p.B = B; p.x = x; p.h = h; p.beta = beta; p.vx = vx; p.vh = vh; p.dir = vx ? -1 : dir;
   p.out = out; p.dout = dout; p.dot_out = dot_out; p.dot_stride = dot_stride; p.dot_off = dot_off; p.diag_acc = diag_acc;
   p.bad = bad;
-  const long long items = multi ? B * s->n * s->dim : B;  // one item per wave
-  const long long want = (items + s->waves - 1) / s->waves, cap = net->n_cu;  // one 4-wave block per CU
+  // one item per ceil(n / 32) waves (a wave per 32-column tile): 4 or 2 items per block, one 4-wave block per CU
+  const long long items = multi ? B * s->n * s->dim : B, ipb = s->waves / ((s->n + 31) / 32);
+  const long long want = (items + ipb - 1) / ipb, cap = net->n_cu;
   const unsigned grid = (unsigned)(want < cap ? want : cap);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->waves * 64), lds, stream, p);
   PITA_LAUNCH_CHECK();

@@ -85,6 +85,11 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         PITA_WIDE_NO_MFMA is set)."""
         return bool(_lib.lib().pita_egnn_wide_uses_matrix_pipe(self._native(torch.device(device))))
 
+    def jvp_uses_matrix_pipe(self, device):
+        """True when ``jvp`` / ``jacobian_trace`` on ``device`` run on the forward-mode MFMA kernel (22 / 33 / 42
+        particles, unless PITA_WIDE_NO_MFMA is set); the vector-pipe kernel alone computes them otherwise."""
+        return bool(_lib.lib().pita_egnn_wide_jvp_uses_matrix_pipe(self._native(torch.device(device))))
+
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_handle"], state["_handle_key"] = None, None
@@ -150,8 +155,8 @@ class EGNN_dynamics_AD2_cat(nn.Module):
     def jvp(self, h_t, x_t, beta, vx=None, direction=-1, vh=None, want_primal=True, want_tangent=True, dot_out=None,
             dot_col=0, diag_acc=None):
         """(D, dD): the EDM denoiser around this backbone and its forward-mode derivative along ONE direction,
-        dD = J_x D . vx + dD/dh . vh -- same contract as ``EGNN_dynamics.jvp`` (pita_egnn_wide_jvp, fp32 vector-pipe
-        kernel).  With it ``VEReverseSDE(debias_inference=True)`` runs on this backbone: the exact divergence of the
+        dD = J_x D . vx + dD/dh . vh -- same contract as ``EGNN_dynamics.jvp`` (pita_egnn_wide_jvp: the matrix-pipe
+        kernel where ``jvp_uses_matrix_pipe``, the fp32 vector-pipe kernel otherwise).  With it ``VEReverseSDE(debias_inference=True)`` runs on this backbone: the exact divergence of the
         score (utils.py:30-51), grad_x E_theta (energy_net.py:51-62) and dE_theta/dt (sdes.py:218) are assembled from
         dim + 1 such launches per net (sdes.py's forward-mode path)."""
         x_t = _lib.dev_tensor(x_t, "x_t")

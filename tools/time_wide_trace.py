@@ -1,10 +1,13 @@
-"""Timing of trace(J_x D) on the wide EGNN backbone (EGNN_dynamics_AD2_cat, 22 atoms, hidden 64 x 5 layers, attention + tanh,
-condition_beta): the n*d = 66 single-direction launches exactly as VEReverseSDE._denoiser_jacobian_terms issues them against
-the single call EGNN_dynamics_AD2_cat.jacobian_trace (pita_egnn_wide_jacobian_trace), alternating, in one process on one
-device, device-event timing.
-python tools/time_wide_trace.py [--batches 512,2048,4096] [--reps 20] [--warmup 3] [--commit HASH]
+"""Timing of trace(J_x D) on the wide EGNN backbone (EGNN_dynamics_AD2_cat, hidden 64 x 5 layers, attention + tanh,
+condition_beta; --particles 22, 33 or 42 atoms): the n*d single-direction launches exactly as
+VEReverseSDE._denoiser_jacobian_terms issues them against the single call EGNN_dynamics_AD2_cat.jacobian_trace
+(pita_egnn_wide_jacobian_trace), alternating, in one process on one device, device-event timing.
+python tools/time_wide_trace.py [--particles 22] [--batches 512,2048,4096] [--reps 20] [--warmup 3] [--single-only]
+                                [--commit HASH]
 Prints per batch size the median and min-max of both in ms, whether the two traces agree bit for bit, and the difference
-against the loop's own min-max spread.  --commit: recorded in the header (default: git rev-parse of the tree it runs in)."""
+against the loop's own min-max spread.  --single-only: the single call alone (the loop takes n*d times as many launches;
+on the vector pipe at 42 atoms that is seconds per repetition).  PITA_WIDE_NO_MFMA=1 in the environment times the
+vector-pipe kernels.  --commit: recorded in the header (default: git rev-parse of the tree it runs in)."""
 import argparse, os, statistics, subprocess, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,9 +15,11 @@ sys.path.insert(0, ROOT)
 import pita_amd as pa
 from pita_amd.egnn_dynamics_ad2_cat import EGNN_dynamics_AD2_cat
 ap = argparse.ArgumentParser()
+ap.add_argument("--particles", type=int, default=22)
 ap.add_argument("--batches", default="512,2048,4096")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--single-only", action="store_true")
 ap.add_argument("--commit", default=None)
 a = ap.parse_args()
 assert torch.cuda.is_available(), "needs the GPU: a timing taken anywhere else says nothing"
@@ -23,12 +28,14 @@ if commit is None:
     r = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True)
     commit = r.stdout.strip() if r.returncode == 0 else "unknown"
 print(f"tools/time_wide_trace.py  commit {commit}  device {torch.cuda.get_device_name(0)}  torch {torch.__version__}")
-print(f"EGNN_dynamics_AD2_cat(22, 3, hidden_nf=64, n_layers=5, attention, tanh, condition_beta), seeded weights; "
+N, ND = a.particles, 3 * a.particles
+print(f"EGNN_dynamics_AD2_cat({N}, 3, hidden_nf=64, n_layers=5, attention, tanh, condition_beta), seeded weights; "
       f"{a.warmup} warm-up + {a.reps} timed repetitions per path, alternating, device events")
 torch.manual_seed(7)
-net = EGNN_dynamics_AD2_cat(22, 3, hidden_nf=64, n_layers=5, tanh=True, attention=True, condition_beta=True)
+net = EGNN_dynamics_AD2_cat(N, 3, hidden_nf=64, n_layers=5, tanh=True, attention=True, condition_beta=True)
 sde = pa.VEReverseSDE(noise_schedule=None, score_net=None, debias_inference=True)
-assert net.uses_matrix_pipe("cuda:0")
+print(f"forward pass on the matrix pipe: {net.uses_matrix_pipe('cuda:0')}, forward mode on the matrix pipe: "
+      f"{net.jvp_uses_matrix_pipe('cuda:0')}")
 
 
 def timed(fn):
@@ -40,12 +47,20 @@ def timed(fn):
 
 for B in (int(b) for b in a.batches.split(",")):
     gen = torch.Generator().manual_seed(B)
-    x = torch.randn(B, 22, 3, generator=gen)
-    x = (x - x.mean(1, keepdim=True)).reshape(B, 66).cuda()
+    x = torch.randn(B, N, 3, generator=gen)
+    x = (x - x.mean(1, keepdim=True)).reshape(B, ND).cuda()
     h = (torch.rand(B, generator=gen) * 2.0 + 0.05).cuda()
     beta = (torch.rand(B, generator=gen) + 0.5).cuda()
-    loop = lambda: sde._denoiser_jacobian_terms(net, h, x, beta, False)  # (D, trace, jtx, None): 66 launches
+    loop = lambda: sde._denoiser_jacobian_terms(net, h, x, beta, False)  # (D, trace, jtx, None): n*d launches
     single = lambda: net.jacobian_trace(h, x, beta, want_denoiser=True)  # (trace, D): one call
+    s = lambda v: f"median {statistics.median(v):8.3f} (min {min(v):8.3f}, max {max(v):8.3f})"
+    if a.single_only:
+        for _ in range(a.warmup):
+            single()
+        torch.cuda.synchronize()
+        ts = [timed(single)[0] for _ in range(a.reps)]
+        print(f"B={B}: single call {s(ts)} ms", flush=True)
+        continue
     for _ in range(a.warmup):
         loop(); single()
     torch.cuda.synchronize()
@@ -56,11 +71,10 @@ for B in (int(b) for b in a.batches.split(",")):
         ms, (tr_s, D_s) = timed(single)
         t["single"].append(ms)
     same = torch.equal(tr_l, tr_s) and torch.equal(D_l, D_s)
-    s = lambda v: f"median {statistics.median(v):8.3f} (min {min(v):8.3f}, max {max(v):8.3f})"
     gain = statistics.median(t["loop"]) - statistics.median(t["single"])
     spread = max(t["loop"]) - min(t["loop"])
     verdict = "beyond the loop's spread" if gain > spread else ("within the loop's spread" if gain >= -spread
                                                                 else "SINGLE CALL SLOWER beyond the loop's spread")
-    print(f"B={B}: 66-launch loop {s(t['loop'])} ms | single call {s(t['single'])} ms | loop - single {gain:8.3f} ms "
+    print(f"B={B}: {ND}-launch loop {s(t['loop'])} ms | single call {s(t['single'])} ms | loop - single {gain:8.3f} ms "
           f"(x{statistics.median(t['loop']) / statistics.median(t['single']):.2f}), loop spread {spread:.3f} ms: {verdict} | "
           f"bits {'identical' if same else 'DIFFER'}", flush=True)
