@@ -148,6 +148,10 @@ int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net);
  * 160 KB, PITA_WIDE_NO_MFMA unset), 0 when on the vector-pipe kernel alone (13, 55 particles and every shape
  * pita_egnn_wide_uses_matrix_pipe is 0 for) */
 int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net);
+/* 1 when pita_egnn_wide_vjp runs this handle's reverse-mode sweep on the matrix-pipe kernel
+ * (csrc/egnn_wide_mfma_vjp_kernel.hip: instantiated for 22, 33, 42 particles x 3, LDS need within a workgroup's 160 KB,
+ * PITA_WIDE_NO_MFMA unset), 0 when on the vector-pipe kernel alone */
+int pita_egnn_wide_vjp_uses_matrix_pipe(const pita_egnn_wide_t* net);
 /* what = 0: vel[B, n*d] = backbone(t[B], x[B, n*d], beta[B]) (mean-free); 1: denoiser D_theta(h = t, x); 2: score */
 int pita_egnn_wide_eval(pita_egnn_wide_t* net, int what, const float* t, const float* x, const float* beta /*nullable*/,
                         float* out, int64_t B, void* stream);
@@ -179,8 +183,12 @@ int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const float* x, co
 /* Reverse-mode derivative of the same denoiser (arguments as pita_egnn_vjp): vjp = J_x D(h, x)^T cot for a per-walker
  * cotangent (null: x itself -- grad_x E_theta = ((1 + c_s) x - D - J_x D^T x)/h, which the reference takes from autograd,
  * pita/src/models/components/energy_net.py:51-62), out = D (nullable), dot_h (nullable) = <cot, dD/dh> (the h-derivative
- * term of dE_theta/dt, sdes.py:218) -- ONE launch instead of dim + 1 forward-mode launches.  fp32 vector-pipe kernel
- * with per-layer checkpoints in a handle-owned scratch (csrc/egnn_wide_kernel.hip: egnn_wide_vjp_kernel). */
+ * term of dE_theta/dt, sdes.py:218) -- ONE sweep instead of dim + 1 forward-mode launches, with per-layer checkpoints
+ * in a handle-owned scratch.  Matrix-pipe kernel (csrc/egnn_wide_mfma_vjp_kernel.hip: f16 two-piece primal, exact
+ * bf16 x 3 adjoint products) for 22, 33 and 42 particles (pita_egnn_wide_vjp_uses_matrix_pipe), then the fp32 vector-pipe
+ * kernel (csrc/egnn_wide_kernel.hip: egnn_wide_vjp_kernel) on exactly the walkers whose primal left the f16 range -- they
+ * get out, vjp and dot_h from it; the vector-pipe kernel alone for every other shape.  A walker's bits do not depend on
+ * B, on its place in the batch or on the run. */
 int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta /*nullable*/,
                        const float* cot /*nullable*/, float* out /*nullable*/, float* vjp, float* dot_h /*nullable*/,
                        int64_t B, void* stream);

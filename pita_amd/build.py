@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpita_hip.so")
-SOURCES = ["abi.hip", "energy_kernels.hip", "ring_kernels.hip", "ff_kernel.hip", "egnn_kernel.hip", "egnn_wide_kernel.hip", "egnn_wide_mfma_kernel.hip", "egnn_wide_mfma_jvp_kernel.hip", "egnn_jvp_kernel.hip", "egnn_vjp_kernel.hip", "egnn_div_kernel.hip", "fk_kernels.hip", "mlp_kernel.hip", "mlp_jac_kernel.hip", "sampler_kernels.hip"]
+SOURCES = ["abi.hip", "energy_kernels.hip", "ring_kernels.hip", "ff_kernel.hip", "egnn_kernel.hip", "egnn_wide_kernel.hip", "egnn_wide_mfma_kernel.hip", "egnn_wide_mfma_jvp_kernel.hip", "egnn_wide_mfma_vjp_kernel.hip", "egnn_jvp_kernel.hip", "egnn_vjp_kernel.hip", "egnn_div_kernel.hip", "fk_kernels.hip", "mlp_kernel.hip", "mlp_jac_kernel.hip", "sampler_kernels.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FALLBACK_OBJECTS = []  # sources whose optional per-file flags the toolchain rejected in this build
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -18,6 +18,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
 # effect on the other kernels: measured on the debiased and the fused-sampler bench legs.)
 PER_FILE_FLAGS = {"egnn_wide_mfma_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                   "egnn_wide_mfma_jvp_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                  "egnn_wide_mfma_vjp_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                   # reverse-mode kernel (one wave per SIMD, resident weight fragments parked in AGPRs): 5.74 -> 5.22 ms
                   "egnn_vjp_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # REQUIRED per-file flags (correctness, never dropped by the retry below).  None today.  Round 5's walker-resident trace

@@ -1,6 +1,6 @@
 // Native handle behind pita_egnn_wide_t, shared by the two kernels that serve it: the vector-pipe kernel
 // (egnn_wide_kernel.hip: any hidden_nf <= 64, any particle count <= 64) and the matrix-pipe kernel
-// (egnn_wide_mfma_kernel.hip: the particle systems it is instantiated for).
+// (egnn_wide_mfma_kernel.hip, with its forward- and reverse-mode siblings: the particle systems they are instantiated for).
 #pragma once
 #include "common.h"
 
@@ -25,6 +25,13 @@ struct pita_egnn_wide {
   size_t jdiag_bytes = 0;
   float* d_vjp_ws = nullptr;  // reverse-mode kernel (vector pipe): per-wave checkpoints of the forward sweep
   size_t vjp_ws_bytes = 0;
+  // reverse-mode kernel on the matrix pipe (egnn_wide_mfma_vjp_kernel.hip)
+  unsigned* d_m16t = nullptr;   // [L][7 matrices][2 x 2 blocks] bf16 x 3 fragments of the unscaled transposes
+  float* d_vecs64t = nullptr;   // [L][w_r 64 | w_e 64] unscaled, fragment order
+  float* d_vjp_ck = nullptr;    // checkpoints of the forward sweep, one region per resident item slot
+  size_t vjp_ck_bytes = 0;
+  int* d_vmark = nullptr;       // [B] walkers left to the vector-pipe kernel; one flag word sits behind them
+  size_t vmark_bytes = 0;
 };
 
 namespace pita {
@@ -48,5 +55,12 @@ int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float*
 // the denoiser; bad: device [B * n*d] ints, zeroed by the caller, one per item
 int wide64_jvp_multi(pita_egnn_wide* net, const float* h, const float* x, const float* beta, float* out, float* diag,
                      int* bad, long long B, hipStream_t stream);
+// 1 when the reverse-mode kernel on the matrix pipe has an instantiation for the net's particle system whose LDS fits
+int wide64_vjp_available(const pita_egnn_wide* net);
+// reverse-mode sweep on the matrix pipe (egnn_wide_mfma_vjp_kernel.hip); returns 1 when the particle system has no
+// instantiation; mark: device [B] ints and flag: one int, zeroed by the caller: set to 1 for the walkers left to the
+// vector-pipe kernel / when there is one
+int wide64_vjp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* cot, float* out,
+               float* vjp, float* dot_h, int* mark, int* flag, long long B, hipStream_t stream);
 void wide64_release(pita_egnn_wide* net);
 }  // namespace pita

@@ -661,6 +661,9 @@ struct WideVjpParams {
   float* vjp;        // [B, n*dim]
   float* dot_h;      // nullable [B]
   float* ws;         // checkpoints: [wave slot][L][2 n 64 + n 4]
+  // repair mode behind the matrix-pipe kernel (egnn_wide_mfma_vjp_kernel.hip); mark null: every walker, as ever
+  const int* mark;   // nullable [B]: compute and write only the walkers marked 1
+  const int* flag;   // with mark: 0 = the matrix-pipe launch marked nobody, return at once
 };
 
 namespace {
@@ -688,7 +691,9 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
   float* ws = q.ws + (size_t)(blockIdx.x * waves + wave) * p.L * ck_layer;
   const bool want_h = q.dot_h != nullptr;
   const long long nw = (long long)gridDim.x * waves;
+  if (q.mark && *q.flag == 0) return;  // nothing to repair
   for (long long w = (long long)blockIdx.x * waves + wave; w < p.B; w += nw) {
+    if (q.mark && q.mark[w] == 0) continue;  // wave-uniform
     const float hval = p.t[w];
     const float bet = p.has_beta ? p.beta[w] : 0.f;
     const float c_s = 1.0f / (1.0f + hval), c_in = 1.0f / sqrtf(1.0f + hval), sh = sqrtf(hval);
@@ -1052,6 +1057,10 @@ extern "C" int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net) 
   return (pita_egnn_wide_uses_matrix_pipe(net) && wide64_jvp_available(net)) ? 1 : 0;
 }
 
+extern "C" int pita_egnn_wide_vjp_uses_matrix_pipe(const pita_egnn_wide_t* net) {
+  return (pita_egnn_wide_uses_matrix_pipe(net) && wide64_vjp_available(net)) ? 1 : 0;
+}
+
 extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
   if (!net) return PITA_OK;
   PitaDeviceGuard guard(net->device);
@@ -1241,7 +1250,9 @@ extern "C" int pita_egnn_wide_sampler_run(pita_egnn_wide_t* net, float* x, int64
                      p, st);
 }
 
-// Reverse-mode derivative of the denoiser around the wide backbone (see egnn_wide_vjp_kernel); arguments as pita_egnn_vjp
+// Reverse-mode derivative of the denoiser around the wide backbone; arguments as pita_egnn_vjp.  Matrix-pipe kernel first
+// where pita_egnn_wide_vjp_uses_matrix_pipe (egnn_wide64_vjp_kernel); it marks the walkers whose primal left the f16 range
+// and the vector-pipe kernel (egnn_wide_vjp_kernel) then computes exactly those; the vector-pipe kernel alone otherwise.
 extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta, const float* cot,
                                   float* out, float* vjp, float* dot_h, int64_t B, void* stream) {
   PITA_REQUIRE(net && B >= 0, "pita_egnn_wide_vjp: bad argument");
@@ -1255,6 +1266,14 @@ extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const f
   p = wide_params(net, B, 1);
   p.x = x; p.t = h; p.beta = beta; p.out = out;
   q.cot = cot; q.vjp = vjp; q.dot_h = dot_h;
+  if (pita_egnn_wide_vjp_uses_matrix_pipe(net)) {
+    const size_t need = sizeof(int) * (size_t)B;
+    PITA_HIP_CHECK(grow_scratch(net->d_vmark, net->vmark_bytes, need, st, sizeof(int)));
+    PITA_HIP_CHECK(hipMemsetAsync(net->d_vmark, 0, need + sizeof(int), st));
+    const int r64 = wide64_vjp(net, h, x, beta, cot, out, vjp, dot_h, net->d_vmark, net->d_vmark + B, B, st);
+    if (r64 == PITA_OK) { q.mark = net->d_vmark; q.flag = net->d_vmark + B; }
+    else if (r64 != 1) return r64;
+  }
   WideGrid g;  // one wave per SIMD
   const int rc = wide_grid("pita_egnn_wide_vjp", net, sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + WIDE_HP),
                            150 * 1024, 1, B, g);

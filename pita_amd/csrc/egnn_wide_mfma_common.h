@@ -1,6 +1,7 @@
 // Shared pieces of the matrix-pipe kernels of the wide EGNN backbone (egnn_wide_mfma_kernel.hip: forward / sampler;
-// egnn_wide_mfma_jvp_kernel.hip: forward-mode derivative): LDS / fragment layout constants, the parameter block, the
-// 64 x 64 dense layer as 2 x 2 blocks of the f16 two-piece MFMA tile.
+// egnn_wide_mfma_jvp_kernel.hip: forward-mode derivative; egnn_wide_mfma_vjp_kernel.hip: reverse-mode sweep): LDS / fragment
+// layout constants, the parameter block, the 64 x 64 dense layer as 2 x 2 blocks of the f16 two-piece MFMA tile, the item
+// fence and the SiLU with its derivative of the two derivative kernels.
 #pragma once
 #include "egnn_common.h"
 #include "egnn_wide_common.h"
@@ -13,6 +14,10 @@ constexpr int W64_MAT_W = 4 * MAT_WH;  // words per 64 x 64 matrix: blocks [out 
 // per-layer vectors, 64 floats each in fragment order [block][hh][r] unless noted
 enum { WV_WRE = 0 /* 128 floats: [block][w_r 32 | w_e 32], natural order (A operand of the f32 k-step) */, WV_B1 = 2, WV_B2,
        WV_WATT, WV_BC1, WV_WC2, WV_BN1, WV_BN2, WV_COUNT };
+// reverse-mode kernel: bf16 x 3 fragments (WFrag<1>) of the UNSCALED transposes, same [out block][in block] order, and per
+// layer the unscaled w_r | w_e in fragment order
+constexpr int W64T_MAT_W = 4 * MAT_W;
+constexpr int W64T_VEC_F = 128;
 constexpr int W64_HEAD_F = 128;                     // emb_t, emb_beta (fragment order)
 constexpr int W64_LAYER_F = WV_COUNT * 64 + 4;      // + b_att
 
@@ -111,6 +116,48 @@ __device__ __forceinline__ void lds_store16(float* dst, const f32x16& v) {
   f32x4* d = reinterpret_cast<f32x4*>(dst);
 #pragma unroll
   for (int q = 0; q < 4; ++q) d[q] = f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+}
+
+// orders an item's LDS tables between their writers and readers: the item is one wave's (NT == 1) or NT waves' of the
+// block (a block barrier; every wave of the block reaches each one the same number of times)
+template <int NT>
+__device__ __forceinline__ void item_fence() {
+  if constexpr (NT == 1) wave_lds_fence();
+  else __syncthreads();
+}
+
+// SiLU of egnn_common.h's PREC 2 forms with the derivative: in v = kS z (UNSCALE: the accumulator 16 kS z), out
+// y = kS silu(z) in place and g = d silu / dz = s + (y / kS)(1 - s) with s the sigmoid the primal computed anyway
+template <bool UNSCALE>
+__device__ __forceinline__ void silu16_d(f32x16& m, f32x16& g) {
+  const f32x2 c = {1.0f / F16_SX, 1.0f / F16_SX};
+  constexpr float kSi = 1.0f / SILU_PRESCALE;
+  f32x2 v[8], e[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    v[q] = f32x2{m[2 * q], m[2 * q + 1]};
+    if (UNSCALE) v[q] = v[q] * F16_UNSCALE;
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    e[q].x = __builtin_amdgcn_exp2f(v[q].x);
+    e[q].y = __builtin_amdgcn_exp2f(v[q].y);
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) e[q] = __builtin_elementwise_fma(e[q], c, c);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    e[q].x = __builtin_amdgcn_rcpf(e[q].x);
+    e[q].y = __builtin_amdgcn_rcpf(e[q].y);
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const f32x2 y = v[q] * e[q];
+    const f32x2 one = {1.0f, 1.0f};
+    const f32x2 gq = __builtin_elementwise_fma(y * kSi, one - e[q], e[q]);
+    m[2 * q] = y.x; m[2 * q + 1] = y.y;
+    g[2 * q] = gq.x; g[2 * q + 1] = gq.y;
+  }
 }
 
 }  // namespace pita

@@ -55,48 +55,6 @@ struct Wide64JvpCfg {
   }
 };
 
-// orders an item's LDS tables between their writers and readers: the item is one wave's (NT == 1) or NT waves' of the
-// block (a block barrier; every wave of the block reaches each one the same number of times)
-template <int NT>
-__device__ __forceinline__ void item_fence() {
-  if constexpr (NT == 1) wave_lds_fence();
-  else __syncthreads();
-}
-
-// SiLU of egnn_common.h's PREC 2 forms with the derivative: in v = kS z (UNSCALE: the accumulator 16 kS z), out
-// y = kS silu(z) in place and g = d silu / dz = s + (y / kS)(1 - s) with s the sigmoid the primal computed anyway
-template <bool UNSCALE>
-__device__ __forceinline__ void silu16_d(f32x16& m, f32x16& g) {
-  const f32x2 c = {1.0f / F16_SX, 1.0f / F16_SX};
-  constexpr float kSi = 1.0f / SILU_PRESCALE;
-  f32x2 v[8], e[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    v[q] = f32x2{m[2 * q], m[2 * q + 1]};
-    if (UNSCALE) v[q] = v[q] * F16_UNSCALE;
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    e[q].x = __builtin_amdgcn_exp2f(v[q].x);
-    e[q].y = __builtin_amdgcn_exp2f(v[q].y);
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) e[q] = __builtin_elementwise_fma(e[q], c, c);
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    e[q].x = __builtin_amdgcn_rcpf(e[q].x);
-    e[q].y = __builtin_amdgcn_rcpf(e[q].y);
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const f32x2 y = v[q] * e[q];
-    const f32x2 one = {1.0f, 1.0f};
-    const f32x2 gq = __builtin_elementwise_fma(y * kSi, one - e[q], e[q]);
-    m[2 * q] = y.x; m[2 * q + 1] = y.y;
-    g[2 * q] = gq.x; g[2 * q + 1] = gq.y;
-  }
-}
-
 // MULTI: the work items are (walker, unit direction) pairs, item = walker * N*DIM + direction (adjacent items share a
 // walker's inputs), each computed exactly as the single-direction launch with vx = vh = null computes it; the item's
 // diagonal entry dD[dir] goes to its own slot (plain store), the item of direction 0 writes the denoiser row; vx, vh, dir,

@@ -398,6 +398,10 @@ int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
   unsigned* hm = new unsigned[n_m]();
   float* hv = new float[n_v]();
   float* hes = new float[(size_t)n * 64]();
+  // reverse-mode kernel: the unscaled transposes as bf16 x 3 fragments, unscaled w_r / w_e in fragment order
+  const size_t n_mt = (size_t)L * WM_COUNT * W64T_MAT_W, n_vt = (size_t)L * W64T_VEC_F;
+  unsigned* hmt = new unsigned[n_mt]();
+  float* hvt = new float[n_vt]();
   const float kS = SILU_PRESCALE, kSi = 1.0f / SILU_PRESCALE, up = F16_SX * F16_SW, dn = 1.0f / F16_SX;
   auto f16_bits = [](float v) { _Float16 h = (_Float16)v; unsigned short u; memcpy(&u, &h, 2); return (unsigned)u; };
   // block (ob, kb) of F16_SW sc M[:, col0 : col0 + H] as a WFrag<2> fragment; rows / columns beyond H are zero
@@ -420,6 +424,28 @@ int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
   auto pack_mat = [&](unsigned* layer, int mat, const float* M, int ld, int col0, float sc) {
     for (int ob = 0; ob < 2; ++ob)
       for (int kb = 0; kb < 2; ++kb) pack_block(layer + ((size_t)mat * 4 + ob * 2 + kb) * MAT_WH, M, ld, col0, ob, kb, sc);
+  };
+  // the transpose of M[:, col0 : col0 + H] as four WFrag<1> blocks: three bf16 pieces cut by truncation (exact split)
+  auto trunc16 = [](float v) { unsigned u; memcpy(&u, &v, 4); u &= 0xFFFF0000u; float o; memcpy(&o, &u, 4); return o; };
+  auto hi16 = [](float v) { unsigned u; memcpy(&u, &v, 4); return u >> 16; };
+  auto pack_mat_t = [&](unsigned* layer, int mat, const float* M, int ld, int col0) {
+    for (int ob = 0; ob < 2; ++ob)
+      for (int kb = 0; kb < 2; ++kb) {
+        unsigned* dst = layer + (size_t)mat * W64T_MAT_W + (size_t)(ob * 2 + kb) * MAT_W;
+        for (int lane = 0; lane < 64; ++lane)
+          for (int st = 0; st < 2; ++st)
+            for (int qd = 0; qd < 4; ++qd) {
+              unsigned pcs[2][3];
+              for (int e = 0; e < 2; ++e) {
+                const int row = ob * 32 + (lane & 31), kin = kb * 32 + kfeat64(8 * st + 2 * qd + e, lane >> 5);
+                const float wv = (row < H && kin < H) ? M[(size_t)kin * ld + col0 + row] : 0.f;
+                const float w1 = trunc16(wv), r1 = wv - w1, w2 = trunc16(r1), r2 = r1 - w2;
+                pcs[e][0] = hi16(w1); pcs[e][1] = hi16(w2); pcs[e][2] = hi16(r2);
+              }
+              for (int pc = 0; pc < 3; ++pc)
+                dst[(((size_t)pc * 2 + st) * 64 + lane) * 4 + qd] = pcs[0][pc] | (pcs[1][pc] << 16);
+            }
+      }
   };
   auto pack_vec = [&](float* dst, const float* v, int stride, float sc) {  // fragment order [block][hh][r]
     for (int b = 0; b < 2; ++b)
@@ -474,11 +500,25 @@ int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
     pack_vec(vl + WV_BN1 * 64, n0b, 1, kS * up);
     pack_vec(vl + WV_BN2 * 64, n2b, 1, up);
     vl[WV_COUNT * 64] = ab ? ab[0] : 0.f;
+    unsigned* mtl = hmt + (size_t)l * WM_COUNT * W64T_MAT_W;
+    pack_mat_t(mtl, WM_WA, e0w, 2 * H + 2, 0);
+    pack_mat_t(mtl, WM_WB, e0w, 2 * H + 2, H);
+    pack_mat_t(mtl, WM_W2, e2w, H, 0);
+    pack_mat_t(mtl, WM_WC1, c0w, H, 0);
+    pack_mat_t(mtl, WM_WN1A, n0w, 2 * H, 0);
+    pack_mat_t(mtl, WM_WN1B, n0w, 2 * H, H);
+    pack_mat_t(mtl, WM_WN2, n2w, H, 0);
+    pack_vec(hvt + (size_t)l * W64T_VEC_F, e0w + 2 * H, 2 * H + 2, 1.0f);
+    pack_vec(hvt + (size_t)l * W64T_VEC_F + 64, e0w + 2 * H + 1, 2 * H + 2, 1.0f);
   }
   hipError_t e = hipMalloc(&net->d_m16h, n_m * sizeof(unsigned));
   if (e == hipSuccess) e = hipMalloc(&net->d_vecs64, n_v * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&net->d_est64, (size_t)n * 64 * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&net->d_flag, sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&net->d_m16t, n_mt * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(&net->d_vecs64t, n_vt * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(net->d_m16t, hmt, n_mt * sizeof(unsigned), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(net->d_vecs64t, hvt, n_vt * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(net->d_m16h, hm, n_m * sizeof(unsigned), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(net->d_vecs64, hv, n_v * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(net->d_est64, hes, (size_t)n * 64 * sizeof(float), hipMemcpyHostToDevice);
@@ -491,6 +531,8 @@ int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
   delete[] hm;
   delete[] hv;
   delete[] hes;
+  delete[] hmt;
+  delete[] hvt;
   if (e != hipSuccess) {
     wide64_release(net);
     return fail(PITA_EHIP, "pita_egnn_wide_create: matrix-pipe weights: %s", hipGetErrorString(e));
@@ -506,6 +548,16 @@ void wide64_release(pita_egnn_wide* net) {
   (void)hipFree(net->d_bk);
   (void)hipFree(net->d_flag);
   (void)hipFree(net->d_jbad);
+  (void)hipFree(net->d_m16t);
+  (void)hipFree(net->d_vecs64t);
+  (void)hipFree(net->d_vjp_ck);
+  (void)hipFree(net->d_vmark);
+  net->d_m16t = nullptr;
+  net->d_vecs64t = nullptr;
+  net->d_vjp_ck = nullptr;
+  net->vjp_ck_bytes = 0;
+  net->d_vmark = nullptr;
+  net->vmark_bytes = 0;
   net->d_jbad = nullptr;
   net->jbad_bytes = 0;
   net->d_flag = nullptr;

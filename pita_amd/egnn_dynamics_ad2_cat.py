@@ -90,6 +90,11 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         particles, unless PITA_WIDE_NO_MFMA is set); the vector-pipe kernel alone computes them otherwise."""
         return bool(_lib.lib().pita_egnn_wide_jvp_uses_matrix_pipe(self._native(torch.device(device))))
 
+    def vjp_uses_matrix_pipe(self, device):
+        """True when ``vjp`` on ``device`` runs its reverse-mode sweep on the MFMA kernel (22 / 33 / 42 particles, unless
+        PITA_WIDE_NO_MFMA is set); the vector-pipe kernel alone computes it otherwise."""
+        return bool(_lib.lib().pita_egnn_wide_vjp_uses_matrix_pipe(self._native(torch.device(device))))
+
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_handle"], state["_handle_key"] = None, None
