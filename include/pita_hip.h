@@ -51,6 +51,9 @@ int pita_device_count(void);
 /* ---------------------------------------------------------------- target energies (K1-K3)
  * All return log-density = -E/T (the reference convention, base_energy_function.py:149) and,
  * when force != NULL, force = d logp / dx.
+ * Accepted shapes of the pair targets and their fused descents: 2 <= n_particles <= 256, n_dim 1, 2 or 3 (else
+ * PITA_EINVAL); every one of them is served (LJ13, LJ55 and DW4 by kernels of their own).  B = 0 returns PITA_OK and
+ * touches nothing.
  */
 
 /* Lennard-Jones cluster + harmonic oscillator.
@@ -206,7 +209,9 @@ int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float* h, const f
 /* Diagonal Gaussian mixture with equal weights.
  * replaces GMM.__call__ (pita/src/energies/gmm_energy.py:87-90) ->
  * fab GMM.log_prob (fab/fab/target_distributions/gmm.py:71-79,104).
- * means, scales: device [K, dim].  */
+ * means, scales: device [K, dim].  1 <= dim <= 4 (else PITA_EUNSUPPORTED), 1 <= K <= 2048 (else PITA_EINVAL); the
+ * table lives in 4 (2 K dim + K) bytes of dynamic LDS -- 73 728 at K = 2048, dim = 4, which gfx950 launches as it is
+ * (tests/test_pair_shapes_gpu.py calls it).  */
 int pita_gmm_logp_force(const float* x, float* logp, float* force /*nullable*/, int64_t B, int dim,
                         const float* means, const float* scales, int K, float temperature,
                         void* stream);

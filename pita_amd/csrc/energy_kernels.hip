@@ -150,13 +150,15 @@ __global__ void __launch_bounds__(256) pair_energy_kernel(const float* __restric
 // order is fixed.  Halves the pair arithmetic of the ordered-pair kernel above (LJ55: 1 485 instead of 2 970 pairs).
 __device__ __forceinline__ void pair_wave_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// per-dimension particle mean of one walker: lanes i < DIM sum, everyone reads (ms: DIM floats of this walker)
+// per-dimension particle sum of one walker: lane i sums the dimensions i, i + n, ... < DIM (one each when n >= DIM; with
+// fewer particles than dimensions, n = 2 in 3-D, lane 0 also takes dimension 2), sequentially over the particles as
+// pita_em_step's centring does; everyone reads (ms: DIM floats of this walker)
 template <int DIM>
 __device__ __forceinline__ void walker_mean(const float* xw, float* ms, int i, int n, float (&mean)[DIM]) {
-  if (i < DIM) {
+  for (int k = i; k < DIM; k += n) {
     float s = 0.f;
-    for (int j = 0; j < n; ++j) s += xw[j * DIM + i];
-    ms[i] = s;
+    for (int j = 0; j < n; ++j) s += xw[j * DIM + k];
+    ms[k] = s;
   }
   pair_wave_fence();
 #pragma unroll
