@@ -91,6 +91,24 @@ inline hipError_t grow_scratch(T*& buf, size_t& size, size_t bytes, hipStream_t 
   return hipSuccess;
 }
 
+// A device allocation that a handle owns: pointer plus the bytes it was sized for, freed with its owner.  grow() is
+// grow_scratch (a scratch buffer); upload() sizes the buffer once and fills it from the host (a fixed allocation).
+struct DeviceBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { (void)hipFree(ptr); }
+  template <class T>
+  T* as() const { return static_cast<T*>(ptr); }
+  hipError_t grow(size_t need, hipStream_t stream, size_t tail = 0) { return grow_scratch(ptr, bytes, need, stream, tail); }
+  hipError_t upload(const void* host, size_t n) {
+    const hipError_t e = grow(n, nullptr);
+    return e != hipSuccess ? e : hipMemcpy(ptr, host, n, hipMemcpyHostToDevice);
+  }
+};
+
 // ---- device math with explicit accuracy choices
 // exp2/rcp map to single v_exp_f32 / v_rcp_f32 (about 1 ulp); used where the reference applies
 // sigmoid-family activations (relative error ~1e-7, no cancellation).

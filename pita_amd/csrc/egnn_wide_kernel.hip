@@ -18,8 +18,6 @@
 // i-major, j ascending: the reference's index_add order, so per-node sums accumulate in the same order.
 // Throughput is that of the vector pipe (~8e5 walker-forwards/s for 22 atoms, 64 x 5): the LJ / DW4 configurations
 // stay on the MFMA kernel.
-#include <cstdlib>
-
 #include "egnn_wide_common.h"
 
 namespace pita {
@@ -42,31 +40,15 @@ struct WideLayer {
 };
 constexpr int WIDE_HEAD = 128;  // emb_t[64], emb_beta[64] in front of the layers
 
-struct WideParams {
-  const float* w;
-  const float* estatic;
-  int n, dim, H, L, attention, tanh_on, has_beta;
-  float coord_scale;
-  long long B;
-  int mode;  // 0 backbone forward (t = its time input), 1 denoiser, 2 score (t = h = sigma^2)
-  const float* x;
-  const float* t;
-  const float* beta;
-  float* out;
-  int only_bad;  // recompute only the walkers whose `out` holds a non-finite value (repair pass behind the matrix-pipe kernel)
-  // mode 3: n_steps Euler-Maruyama steps of the not-debiased reverse SDE in one launch (pita_egnn_wide_sampler_run)
-  float* xs;               // [B, n*dim] walkers, in place
-  const float* x_backup;   // only_bad: the walkers as they were before the matrix-pipe launch
-  const float* step_tab;   // [n_steps][PITA_STEP_STRIDE]
-  int n_steps;
-  const float* noise;      // nullable [n_steps, B, n*dim]
-  unsigned long long seed, walker_offset;
-  long long step0;
-  int remove_mean;
-  double* stats_out;       // nullable [n_steps][4]
-  const int* bad_from;     // only_bad: [B*n] first step whose moments the matrix-pipe launch left to this one
-  const int* bad_flag;     // only_bad, nullable: 0 = the matrix-pipe launch left nothing non-finite, return at once
-};
+// floats of LDS per wave (= walker) of each kernel, read by the kernel and by its launcher; the reverse-mode kernel's
+// checkpoints per wave slot and layer (global scratch): features entering the layer and the node model's pre-activation,
+// [n][64] each, and the positions [n][4].
+// egnn_wide_kernel's is a macro: behind an inlined call the compiler orders three scalar instructions of the sampler
+// instantiations differently, and the device code is pinned instruction by instruction (profiles/r10_wide_host_refactor.txt)
+#define WIDE_PER_WAVE(n, smp) (3 * (n) * WIDE_HP + ((smp) ? 4 : 3) * (n) * 4 + WIDE_HP)
+__host__ __device__ constexpr int wide_jvp_per_wave(int n) { return 5 * n * WIDE_HP + 6 * n * 4 + 2 * WIDE_HP; }
+__host__ __device__ constexpr int wide_vjp_per_wave(int n) { return 5 * n * WIDE_HP + 6 * n * 4 + WIDE_HP; }
+__host__ __device__ constexpr size_t wide_vjp_ck_layer(int n) { return (size_t)2 * n * WIDE_HP + (size_t)n * 4; }
 
 namespace {
 
@@ -162,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) egnn_wide_kernel(WideParams p) {  // t
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = p.n, DIM = p.dim;
-  const int per_wave = 3 * n * WIDE_HP + (SMP ? 4 : 3) * n * 4 + WIDE_HP;
+  const int per_wave = WIDE_PER_WAVE(n, SMP);
   float* hf = lds + wave * per_wave;     // [n][64] node features
   float* At = hf + n * WIDE_HP;          // [n][64] Wa h_i + b1
   float* Bt = At + n * WIDE_HP;          // [n][64] Wb h_j
@@ -366,19 +348,6 @@ __global__ void __launch_bounds__(256, 2) egnn_wide_kernel(WideParams p) {  // t
 // feature -- with a tangent beside every primal quantity: the node features, the partner table Wb dh_j, the positions.
 // A tangent dense layer costs what the primal one does (v_readlane + v_fma per k on the same weight row); the SiLU
 // derivative sigma (1 + z (1 - sigma)) re-uses the primal's sigmoid.  fp32 FMA chains like the primal.
-struct WideJvpParams {
-  WideParams base;       // mode is ignored: the denoiser (mode 1) is differentiated
-  const float* vx;       // nullable [B, n*dim]: position direction; null -> unit vector e_dir (dir >= 0) or zero (dir < 0)
-  const float* vh;       // nullable [B]: direction in h
-  int dir;
-  float* dout;           // nullable [B, n*dim]
-  float* dot_out;        // nullable: dot_out[b * dot_stride + dot_off] = <x_b, dD_b>
-  long long dot_stride, dot_off;
-  float* diag_acc;       // nullable: diag_acc[b] += dD[b, dir]; MULTI: [n*dim, B], diag_acc[dir * B + b] = dD[b, dir]
-  const int* only_bad;   // nullable [B] (MULTI: [B * n*dim], one per item): process only what the matrix-pipe kernel
-                         // flagged (egnn_wide_mfma_jvp_kernel.hip)
-};
-
 namespace {
 
 // silu(z) and d silu / dz from one sigmoid
@@ -454,7 +423,7 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = p.n, DIM = p.dim;
-  const int per_wave = 5 * n * WIDE_HP + 6 * n * 4 + 2 * WIDE_HP;
+  const int per_wave = wide_jvp_per_wave(n);
   float* hf = lds + wave * per_wave;     // [n][64] node features
   float* At = hf + n * WIDE_HP;          // [n][64] Wa h_i + b1
   float* Bt = At + n * WIDE_HP;          // [n][64] Wb h_j
@@ -655,17 +624,6 @@ __global__ void __launch_bounds__(256) egnn_wide_trace_reduce_kernel(const float
 // per-wave LDS tables -- edges are swept one at a time by the whole wave, so those read-modify-writes never collide.
 // Every edge is recomputed with its SiLU derivatives; the transposed products read the natural-order weight copies
 // (W2^T and Wc1^T rows in registers beside the forward rows: one wave per SIMD).
-struct WideVjpParams {
-  WideParams base;   // x, t (= h), beta, out (nullable: the denoiser)
-  const float* cot;  // nullable [B, n*dim]: cotangent (null: x)
-  float* vjp;        // [B, n*dim]
-  float* dot_h;      // nullable [B]
-  float* ws;         // checkpoints: [wave slot][L][2 n 64 + n 4]
-  // repair mode behind the matrix-pipe kernel (egnn_wide_mfma_vjp_kernel.hip); mark null: every walker, as ever
-  const int* mark;   // nullable [B]: compute and write only the walkers marked 1
-  const int* flag;   // with mark: 0 = the matrix-pipe launch marked nobody, return at once
-};
-
 namespace {
 
 template <int HK>
@@ -674,7 +632,7 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = p.n, DIM = p.dim;
-  const int per_wave = 5 * n * WIDE_HP + 6 * n * 4 + WIDE_HP;
+  const int per_wave = wide_vjp_per_wave(n);
   float* hf = lds + wave * per_wave;     // [n][64] features entering the layer
   float* At = hf + n * WIDE_HP;          // [n][64] Wa h_i + b1
   float* Bt = At + n * WIDE_HP;          // [n][64] Wb h_j
@@ -687,7 +645,7 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
   float* pbn = pb + n * 4;               // [n][4] adjoint of the positions entering it (being summed)
   float* p0b = pbn + n * 4;              // [n][4] adjoint of the input geometry (edge attribute of every layer, and -u)
   float* bc = p0b + n * 4;               // [64] broadcast slot of the dense layers
-  const size_t ck_layer = (size_t)2 * n * WIDE_HP + (size_t)n * 4;
+  const size_t ck_layer = wide_vjp_ck_layer(n);
   float* ws = q.ws + (size_t)(blockIdx.x * waves + wave) * p.L * ck_layer;
   const bool want_h = q.dot_h != nullptr;
   const long long nw = (long long)gridDim.x * waves;
@@ -930,12 +888,67 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
 
 using namespace pita;
 
+
 extern "C" int64_t pita_egnn_wide_num_weights(const pita_egnn_wide_config* c) {
   if (!c) return PITA_EINVAL;
-  const int64_t H = c->hidden_nf, nf = c->n_static + 1 + (c->condition_beta ? 1 : 0);
-  int64_t per_layer = (H * (2 * H + 2) + H) + (H * H + H) + (H * 2 * H + H) + (H * H + H) + (H * H + H) + H;
-  if (c->attention) per_layer += H + 1;
-  return (H * nf + H) + (nf * H + nf) + c->n_layers * per_layer;
+  return wide_weights(*c, nullptr).count;
+}
+
+extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
+  if (!net) return PITA_OK;
+  PitaDeviceGuard guard(net->device);
+  delete net;  // the handle's buffers free themselves
+  return PITA_OK;
+}
+
+// packs the vector-pipe weights (WideLayer) and the static embedding he: host [n][64]
+static int wide_prepare(pita_egnn_wide* net, const WideWeights& W, const float* h_initial, std::vector<float>& he) {
+  const int H = W.H, L = net->cfg.n_layers, ns = W.ns, nf = W.nf, n = net->cfg.n_particles;
+  std::vector<float> hw(WIDE_HEAD + (size_t)L * WideLayer::SIZE);
+  for (int f = 0; f < H; ++f) {
+    hw[f] = W.emb_w[f * nf + ns];
+    hw[64 + f] = net->cfg.condition_beta ? W.emb_w[f * nf + ns + 1] : 0.f;
+    for (int i = 0; i < n; ++i) {
+      double s = W.emb_b[f];
+      for (int k = 0; k < ns; ++k) s += (double)W.emb_w[f * nf + k] * (double)h_initial[i * ns + k];
+      he[i * WIDE_HP + f] = (float)s;
+    }
+  }
+  // the transposed copy dst[k][f] = M[f][col0 + k] at `at`, the natural one dst[f][k] behind the vectors
+  auto put = [&](float* wl, int at, const float* M, int ld, int col0) {
+    for (int k = 0; k < H; ++k)
+      for (int f = 0; f < H; ++f) {
+        wl[at + k * WIDE_HP + f] = M[f * ld + col0 + k];
+        wl[WideLayer::NAT + at + f * WIDE_HP + k] = M[f * ld + col0 + k];
+      }
+  };
+  for (int l = 0; l < L; ++l) {
+    float* wl = hw.data() + WIDE_HEAD + (size_t)l * WideLayer::SIZE;
+    const WideLayerW& v = W.layer[l];
+    put(wl, WideLayer::WA, v.e0w, 2 * H + 2, 0);
+    put(wl, WideLayer::WB, v.e0w, 2 * H + 2, H);
+    put(wl, WideLayer::W2, v.e2w, H, 0);
+    put(wl, WideLayer::WC1, v.c0w, H, 0);
+    put(wl, WideLayer::WN1A, v.n0w, 2 * H, 0);
+    put(wl, WideLayer::WN1B, v.n0w, 2 * H, H);
+    put(wl, WideLayer::WN2, v.n2w, H, 0);
+    for (int f = 0; f < H; ++f) {
+      wl[WideLayer::WR + f] = v.e0w[f * (2 * H + 2) + 2 * H];
+      wl[WideLayer::WE + f] = v.e0w[f * (2 * H + 2) + 2 * H + 1];
+      wl[WideLayer::B1 + f] = v.e0b[f];
+      wl[WideLayer::B2 + f] = v.e2b[f];
+      wl[WideLayer::WATT + f] = v.aw ? v.aw[f] : 0.f;
+      wl[WideLayer::BC1 + f] = v.c0b[f];
+      wl[WideLayer::WC2 + f] = v.c2w[f];
+      wl[WideLayer::BN1 + f] = v.n0b[f];
+      wl[WideLayer::BN2 + f] = v.n2b[f];
+    }
+    wl[WideLayer::BATT] = v.ab ? v.ab[0] : 0.f;
+  }
+  hipError_t e = net->w.upload(hw.data(), hw.size() * sizeof(float));
+  if (e == hipSuccess) e = net->estatic.upload(he.data(), he.size() * sizeof(float));
+  if (e != hipSuccess) return fail(PITA_EHIP, "pita_egnn_wide_create: device upload failed: %s", hipGetErrorString(e));
+  return PITA_OK;
 }
 
 extern "C" int pita_egnn_wide_create(pita_egnn_wide_t** out, const pita_egnn_wide_config* cfg, const float* w,
@@ -946,136 +959,35 @@ extern "C" int pita_egnn_wide_create(pita_egnn_wide_t** out, const pita_egnn_wid
                "pita_egnn_wide_create: n_particles in [2, 64], n_dim in [1, 3]");
   PITA_REQUIRE(cfg->n_layers >= 1 && cfg->n_layers <= 16 && cfg->n_static >= 0, "pita_egnn_wide_create: bad layer / feature count");
   PITA_REQUIRE(cfg->n_static == 0 || h_initial, "pita_egnn_wide_create: h_initial missing");
-  PITA_REQUIRE(n_weights == pita_egnn_wide_num_weights(cfg), "pita_egnn_wide_create: got %lld weights, expected %lld",
-               (long long)n_weights, (long long)pita_egnn_wide_num_weights(cfg));
-  const int H = cfg->hidden_nf, L = cfg->n_layers, ns = cfg->n_static, n = cfg->n_particles;
-  const int nf = ns + 1 + (cfg->condition_beta ? 1 : 0);
-  const size_t n_w = WIDE_HEAD + (size_t)L * WideLayer::SIZE;
-  float* hw = new float[n_w]();
-  float* he = new float[(size_t)n * WIDE_HP]();
-  const float* q = w;
-  const float* emb_w = q; q += H * nf;
-  const float* emb_b = q; q += H;
-  q += nf * H + nf;  // embedding_out: dead (h_final is discarded, egnn_dynamics_ad2_cat.py:187)
-  for (int f = 0; f < H; ++f) {
-    hw[f] = emb_w[f * nf + ns];
-    hw[64 + f] = cfg->condition_beta ? emb_w[f * nf + ns + 1] : 0.f;
-    for (int i = 0; i < n; ++i) {
-      double s = emb_b[f];
-      for (int k = 0; k < ns; ++k) s += (double)emb_w[f * nf + k] * (double)h_initial[i * ns + k];
-      he[i * WIDE_HP + f] = (float)s;
-    }
-  }
-  auto put_t = [&](float* dst, const float* M, int ld, int col0) {  // dst[k][f] = M[f][col0 + k]
-    for (int k = 0; k < H; ++k)
-      for (int f = 0; f < H; ++f) dst[k * WIDE_HP + f] = M[f * ld + col0 + k];
-  };
-  auto put_n = [&](float* dst, const float* M, int ld, int col0) {  // dst[f][k] = M[f][col0 + k]
-    for (int f = 0; f < H; ++f)
-      for (int k = 0; k < H; ++k) dst[f * WIDE_HP + k] = M[f * ld + col0 + k];
-  };
-  for (int l = 0; l < L; ++l) {
-    float* wl = hw + WIDE_HEAD + (size_t)l * WideLayer::SIZE;
-    const float* e0w = q; q += H * (2 * H + 2);
-    const float* e0b = q; q += H;
-    const float* e2w = q; q += H * H;
-    const float* e2b = q; q += H;
-    const float* n0w = q; q += H * 2 * H;
-    const float* n0b = q; q += H;
-    const float* n2w = q; q += H * H;
-    const float* n2b = q; q += H;
-    const float* c0w = q; q += H * H;
-    const float* c0b = q; q += H;
-    const float* c2w = q; q += H;
-    const float* aw = nullptr; const float* ab = nullptr;
-    if (cfg->attention) { aw = q; q += H; ab = q; q += 1; }
-    put_t(wl + WideLayer::WA, e0w, 2 * H + 2, 0);
-    put_t(wl + WideLayer::WB, e0w, 2 * H + 2, H);
-    put_t(wl + WideLayer::W2, e2w, H, 0);
-    put_t(wl + WideLayer::WC1, c0w, H, 0);
-    put_t(wl + WideLayer::WN1A, n0w, 2 * H, 0);
-    put_t(wl + WideLayer::WN1B, n0w, 2 * H, H);
-    put_t(wl + WideLayer::WN2, n2w, H, 0);
-    put_n(wl + WideLayer::WAN, e0w, 2 * H + 2, 0);
-    put_n(wl + WideLayer::WBN, e0w, 2 * H + 2, H);
-    put_n(wl + WideLayer::W2N, e2w, H, 0);
-    put_n(wl + WideLayer::WC1N, c0w, H, 0);
-    put_n(wl + WideLayer::WN1AN, n0w, 2 * H, 0);
-    put_n(wl + WideLayer::WN1BN, n0w, 2 * H, H);
-    put_n(wl + WideLayer::WN2N, n2w, H, 0);
-    for (int f = 0; f < H; ++f) {
-      wl[WideLayer::WR + f] = e0w[f * (2 * H + 2) + 2 * H];
-      wl[WideLayer::WE + f] = e0w[f * (2 * H + 2) + 2 * H + 1];
-      wl[WideLayer::B1 + f] = e0b[f];
-      wl[WideLayer::B2 + f] = e2b[f];
-      wl[WideLayer::WATT + f] = aw ? aw[f] : 0.f;
-      wl[WideLayer::BC1 + f] = c0b[f];
-      wl[WideLayer::WC2 + f] = c2w[f];
-      wl[WideLayer::BN1 + f] = n0b[f];
-      wl[WideLayer::BN2 + f] = n2b[f];
-    }
-    wl[WideLayer::BATT] = ab ? ab[0] : 0.f;
-  }
+  const WideWeights W = wide_weights(*cfg, w);
+  PITA_REQUIRE(n_weights == W.count, "pita_egnn_wide_create: got %lld weights, expected %lld", (long long)n_weights,
+               (long long)W.count);
   pita_egnn_wide* net = new pita_egnn_wide();
   net->cfg = *cfg;
-  hipError_t e = hipMalloc(&net->d_w, n_w * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&net->d_estatic, (size_t)n * WIDE_HP * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(net->d_w, hw, n_w * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(net->d_estatic, he, (size_t)n * WIDE_HP * sizeof(float), hipMemcpyHostToDevice);
-  delete[] hw;
-  if (e != hipSuccess) {
-    delete[] he;
-    (void)hipFree(net->d_w);
-    (void)hipFree(net->d_estatic);
-    delete net;
-    return fail(PITA_EHIP, "pita_egnn_wide_create: device upload failed: %s", hipGetErrorString(e));
-  }
   int dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess) {
     net->device = dev;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess) net->n_cu = prop.multiProcessorCount;
   }
-  const int rc64 = wide64_prepare(net, w, he);
-  delete[] he;
-  if (rc64 != PITA_OK) {
-    (void)hipFree(net->d_w);
-    (void)hipFree(net->d_estatic);
-    delete net;
-    return rc64;
+  std::vector<float> he((size_t)cfg->n_particles * WIDE_HP);
+  int rc = wide_prepare(net, W, h_initial, he);
+  if (rc == PITA_OK) rc = wide64_prepare(net, W, he.data());
+  if (rc != PITA_OK) {
+    pita_egnn_wide_destroy(net);
+    return rc;
   }
   *out = net;
   return PITA_OK;
 }
 
-extern "C" int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net) {
-  // PITA_WIDE_NO_MFMA (read at every call): A/B against the vector-pipe kernel
-  return (net && net->shape64 && getenv("PITA_WIDE_NO_MFMA") == nullptr) ? 1 : 0;
-}
-
-extern "C" int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net) {
-  return (pita_egnn_wide_uses_matrix_pipe(net) && wide64_jvp_available(net)) ? 1 : 0;
-}
-
-extern "C" int pita_egnn_wide_vjp_uses_matrix_pipe(const pita_egnn_wide_t* net) {
-  return (pita_egnn_wide_uses_matrix_pipe(net) && wide64_vjp_available(net)) ? 1 : 0;
-}
-
-extern "C" int pita_egnn_wide_destroy(pita_egnn_wide_t* net) {
-  if (!net) return PITA_OK;
-  PitaDeviceGuard guard(net->device);
-  wide64_release(net);
-  (void)hipFree(net->d_vjp_ws);
-  (void)hipFree(net->d_jdiag);
-  (void)hipFree(net->d_w);
-  (void)hipFree(net->d_estatic);
-  delete net;
-  return PITA_OK;
-}
+extern "C" int pita_egnn_wide_uses_matrix_pipe(const pita_egnn_wide_t* net) { return wide_plan(net).fwd ? 1 : 0; }
+extern "C" int pita_egnn_wide_jvp_uses_matrix_pipe(const pita_egnn_wide_t* net) { return wide_plan(net).jvp ? 1 : 0; }
+extern "C" int pita_egnn_wide_vjp_uses_matrix_pipe(const pita_egnn_wide_t* net) { return wide_plan(net).vjp ? 1 : 0; }
 
 static WideParams wide_params(const pita_egnn_wide_t* net, long long B, int mode) {
   WideParams p{};
-  p.w = net->d_w; p.estatic = net->d_estatic;
+  p.w = net->w.as<float>(); p.estatic = net->estatic.as<float>();
   p.n = net->cfg.n_particles; p.dim = net->cfg.n_dim; p.H = net->cfg.hidden_nf; p.L = net->cfg.n_layers;
   p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
   p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
@@ -1083,18 +995,19 @@ static WideParams wide_params(const pita_egnn_wide_t* net, long long B, int mode
   return p;
 }
 
-// A vector-pipe launch over B walkers, one walker per wave: per_wave bytes of LDS each, four waves per block halved until
+// A vector-pipe launch over B walkers, one walker per wave: per_wave floats of LDS each, four waves per block halved until
 // a block needs at most block_cap bytes, at most blocks_per_cu blocks per CU
 struct WideGrid {
   int waves;
   size_t lds;
   unsigned grid;
 };
-static int wide_grid(const char* fn, const pita_egnn_wide_t* net, size_t per_wave, size_t block_cap, long long blocks_per_cu,
+static int wide_grid(const char* fn, const pita_egnn_wide_t* net, int per_wave_f, size_t block_cap, long long blocks_per_cu,
                      long long B, WideGrid& g) {
+  const size_t per_wave = sizeof(float) * (size_t)per_wave_f;
   int waves = 4;
   while (waves > 1 && per_wave * waves > block_cap) waves >>= 1;
-  if (per_wave * waves > 150 * 1024)
+  if (per_wave * waves > kWideLdsOneBlock)
     return fail(PITA_EUNSUPPORTED, "%s: %d particles need %zu B of LDS per wave", fn, net->cfg.n_particles, per_wave);
   const long long want = (B + waves - 1) / waves, cap = (long long)net->n_cu * blocks_per_cu;
   g = {waves, per_wave * waves, (unsigned)(want < cap ? want : cap)};
@@ -1121,18 +1034,25 @@ extern "C" int pita_egnn_wide_eval(pita_egnn_wide_t* net, int what, const float*
   p.x = x; p.t = t; p.beta = beta; p.out = out;
   // matrix-pipe kernel first where the particle system has one; the vector-pipe kernel then recomputes the walkers whose
   // result came out non-finite (an activation beyond the f16 range) and returns at once for all others
-  if (pita_egnn_wide_uses_matrix_pipe(net)) {
-    const int rc = wide64_launch(net, what, t, x, beta, out, B, (hipStream_t)stream);
+  if (wide_plan(net).fwd) {
+    const int rc = wide64_forward(net, p, nullptr, (hipStream_t)stream);
     if (rc != PITA_OK) return rc;
     p.only_bad = 1;
-    p.bad_flag = net->d_flag;
+    p.bad_flag = net->flag.as<int>();
   }
-  WideGrid g;  // two blocks per CU inside the 160 KB
-  const int rc = wide_grid("pita_egnn_wide_eval", net, sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 3 * p.n * 4 + WIDE_HP),
-                           72 * 1024, 8, B, g);
+  WideGrid g;
+  const int rc = wide_grid("pita_egnn_wide_eval", net, WIDE_PER_WAVE(p.n, false), kWideLdsTwoBlocks, 8, B, g);
   if (rc != PITA_OK) return rc;
   return wide_launch("pita_egnn_wide_eval", p.H <= 32 ? egnn_wide_kernel<32, false> : egnn_wide_kernel<64, false>, g, p,
                      (hipStream_t)stream);
+}
+
+// the forward-mode marks, one int per item, zeroed: what the matrix-pipe kernel leaves to the vector-pipe one
+static int wide_jvp_marks(pita_egnn_wide_t* net, long long items, hipStream_t st) {
+  const size_t need = sizeof(int) * (size_t)items;
+  PITA_HIP_CHECK(net->jbad.grow(need, st));
+  PITA_HIP_CHECK(hipMemsetAsync(net->jbad.ptr, 0, need, st));
+  return PITA_OK;
 }
 
 // Forward-mode derivative of the denoiser around the wide backbone (egnn_wide_jvp_kernel, behind the matrix-pipe kernel
@@ -1154,20 +1074,16 @@ extern "C" int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const f
   p.x = x; p.t = h; p.beta = beta; p.out = out;
   q.vx = vx; q.vh = vh; q.dir = vx ? -1 : dir; q.dout = dout; q.dot_out = dot_out; q.dot_stride = dot_stride;
   q.dot_off = dot_off; q.diag_acc = diag_acc;
-  // matrix-pipe kernel first where the particle system has one (PITA_WIDE_NO_MFMA: the vector-pipe kernel alone); it
-  // flags the walkers whose primal or tangent left the f16 range and the vector-pipe kernel below computes exactly those
-  if (pita_egnn_wide_uses_matrix_pipe(net)) {
-    const size_t need = sizeof(int) * (size_t)B;
-    PITA_HIP_CHECK(grow_scratch(net->d_jbad, net->jbad_bytes, need, st));
-    PITA_HIP_CHECK(hipMemsetAsync(net->d_jbad, 0, need, st));
-    const int r64 = wide64_jvp(net, h, x, beta, vx, dir, vh, out, dout, dot_out, dot_stride, dot_off, diag_acc, net->d_jbad,
-                               B, st);
-    if (r64 == PITA_OK) q.only_bad = net->d_jbad;
-    else if (r64 != 1) return r64;
+  // matrix-pipe kernel first where the plan has one; it flags the walkers whose primal or tangent left the f16 range and
+  // the vector-pipe kernel below computes exactly those
+  if (wide_plan(net).jvp) {
+    int rc = wide_jvp_marks(net, B, st);
+    if (rc == PITA_OK) rc = wide64_jvp(net, q, false, net->jbad.as<int>(), st);
+    if (rc != PITA_OK) return rc;
+    q.only_bad = net->jbad.as<int>();
   }
   WideGrid g;
-  const int rc = wide_grid("pita_egnn_wide_jvp", net, sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + 2 * WIDE_HP),
-                           150 * 1024, 2, B, g);
+  const int rc = wide_grid("pita_egnn_wide_jvp", net, wide_jvp_per_wave(p.n), kWideLdsOneBlock, 2, B, g);
   if (rc != PITA_OK) return rc;
   return wide_launch("pita_egnn_wide_jvp", p.H <= 32 ? egnn_wide_jvp_kernel<32> : egnn_wide_jvp_kernel<64>, g, q, st);
 }
@@ -1189,24 +1105,21 @@ extern "C" int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float*
   p.x = x; p.t = h; p.beta = beta; p.out = denoiser_out;
   const int ndir = p.n * p.dim;
   const long long items = (long long)B * ndir;
-  PITA_HIP_CHECK(grow_scratch(net->d_jdiag, net->jdiag_bytes, sizeof(float) * (size_t)items, st));
-  q.dir = -1; q.diag_acc = net->d_jdiag;
-  if (pita_egnn_wide_uses_matrix_pipe(net)) {
-    const size_t need = sizeof(int) * (size_t)items;
-    PITA_HIP_CHECK(grow_scratch(net->d_jbad, net->jbad_bytes, need, st));
-    PITA_HIP_CHECK(hipMemsetAsync(net->d_jbad, 0, need, st));
-    const int r64 = wide64_jvp_multi(net, h, x, beta, denoiser_out, net->d_jdiag, net->d_jbad, B, st);
-    if (r64 == PITA_OK) q.only_bad = net->d_jbad;
-    else if (r64 != 1) return r64;
+  PITA_HIP_CHECK(net->jdiag.grow(sizeof(float) * (size_t)items, st));
+  q.dir = -1; q.diag_acc = net->jdiag.as<float>();
+  if (wide_plan(net).jvp) {
+    int rc = wide_jvp_marks(net, items, st);
+    if (rc == PITA_OK) rc = wide64_jvp(net, q, true, net->jbad.as<int>(), st);
+    if (rc != PITA_OK) return rc;
+    q.only_bad = net->jbad.as<int>();
   }
   WideGrid g;
-  int rc = wide_grid("pita_egnn_wide_jacobian_trace", net,
-                     sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + 2 * WIDE_HP), 150 * 1024, 2, items, g);
+  int rc = wide_grid("pita_egnn_wide_jacobian_trace", net, wide_jvp_per_wave(p.n), kWideLdsOneBlock, 2, items, g);
   if (rc != PITA_OK) return rc;
   rc = wide_launch("pita_egnn_wide_jacobian_trace", p.H <= 32 ? egnn_wide_jvp_kernel<32, true> : egnn_wide_jvp_kernel<64, true>,
                    g, q, st);
   if (rc != PITA_OK) return rc;
-  hipLaunchKernelGGL(egnn_wide_trace_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, net->d_jdiag, trace,
+  hipLaunchKernelGGL(egnn_wide_trace_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, q.diag_acc, trace,
                      (long long)B, ndir);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
@@ -1228,23 +1141,21 @@ extern "C" int pita_egnn_wide_sampler_run(pita_egnn_wide_t* net, float* x, int64
   WideParams p = wide_params(net, B, 3);
   p.xs = x; p.step_tab = step_tab; p.n_steps = n_steps; p.noise = noise; p.seed = seed;
   p.walker_offset = walker_offset; p.step0 = step0; p.remove_mean = remove_mean; p.stats_out = stats_out;
-  if (pita_egnn_wide_uses_matrix_pipe(net)) {
+  if (wide_plan(net).fwd) {
     const size_t nx = (size_t)B * p.n * p.dim;
-    PITA_HIP_CHECK(grow_scratch(net->d_bk, net->bk_bytes, sizeof(float) * nx + sizeof(int) * (size_t)B * p.n, st));
-    float* xb = static_cast<float*>(net->d_bk);
+    PITA_HIP_CHECK(net->bk.grow(sizeof(float) * nx + sizeof(int) * (size_t)B * p.n, st));
+    float* xb = net->bk.as<float>();
     int* bad_from = reinterpret_cast<int*>(xb + nx);
     PITA_HIP_CHECK(hipMemcpyAsync(xb, x, sizeof(float) * nx, hipMemcpyDeviceToDevice, st));
-    const int rc = wide64_sampler(net, x, B, step_tab, n_steps, noise, seed, walker_offset, step0, remove_mean, stats_out,
-                                  bad_from, st);
+    const int rc = wide64_forward(net, p, bad_from, st);
     if (rc != PITA_OK) return rc;
     p.only_bad = 1;
     p.x_backup = xb;
     p.bad_from = bad_from;
-    p.bad_flag = net->d_flag;
+    p.bad_flag = net->flag.as<int>();
   }
   WideGrid g;
-  const int rc = wide_grid("pita_egnn_wide_sampler_run", net,
-                           sizeof(float) * (size_t)(3 * p.n * WIDE_HP + 4 * p.n * 4 + WIDE_HP), 72 * 1024, 8, B, g);
+  const int rc = wide_grid("pita_egnn_wide_sampler_run", net, WIDE_PER_WAVE(p.n, true), kWideLdsTwoBlocks, 8, B, g);
   if (rc != PITA_OK) return rc;
   return wide_launch("pita_egnn_wide_sampler_run", p.H <= 32 ? egnn_wide_kernel<32, true> : egnn_wide_kernel<64, true>, g,
                      p, st);
@@ -1266,21 +1177,20 @@ extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const f
   p = wide_params(net, B, 1);
   p.x = x; p.t = h; p.beta = beta; p.out = out;
   q.cot = cot; q.vjp = vjp; q.dot_h = dot_h;
-  if (pita_egnn_wide_vjp_uses_matrix_pipe(net)) {
+  if (wide_plan(net).vjp) {
     const size_t need = sizeof(int) * (size_t)B;
-    PITA_HIP_CHECK(grow_scratch(net->d_vmark, net->vmark_bytes, need, st, sizeof(int)));
-    PITA_HIP_CHECK(hipMemsetAsync(net->d_vmark, 0, need + sizeof(int), st));
-    const int r64 = wide64_vjp(net, h, x, beta, cot, out, vjp, dot_h, net->d_vmark, net->d_vmark + B, B, st);
-    if (r64 == PITA_OK) { q.mark = net->d_vmark; q.flag = net->d_vmark + B; }
-    else if (r64 != 1) return r64;
+    PITA_HIP_CHECK(net->vmark.grow(need, st, sizeof(int)));
+    PITA_HIP_CHECK(hipMemsetAsync(net->vmark.ptr, 0, need + sizeof(int), st));
+    int* mark = net->vmark.as<int>();
+    const int rc = wide64_vjp(net, q, mark, mark + B, st);
+    if (rc != PITA_OK) return rc;
+    q.mark = mark; q.flag = mark + B;
   }
   WideGrid g;  // one wave per SIMD
-  const int rc = wide_grid("pita_egnn_wide_vjp", net, sizeof(float) * (size_t)(5 * p.n * WIDE_HP + 6 * p.n * 4 + WIDE_HP),
-                           150 * 1024, 1, B, g);
+  const int rc = wide_grid("pita_egnn_wide_vjp", net, wide_vjp_per_wave(p.n), kWideLdsOneBlock, 1, B, g);
   if (rc != PITA_OK) return rc;
   // per-wave checkpoints of the forward sweep
-  PITA_HIP_CHECK(grow_scratch(net->d_vjp_ws, net->vjp_ws_bytes,
-                              sizeof(float) * (size_t)g.grid * g.waves * p.L * ((size_t)2 * p.n * WIDE_HP + (size_t)p.n * 4), st));
-  q.ws = net->d_vjp_ws;
+  PITA_HIP_CHECK(net->vjp_ws.grow(sizeof(float) * (size_t)g.grid * g.waves * p.L * wide_vjp_ck_layer(p.n), st));
+  q.ws = net->vjp_ws.as<float>();
   return wide_launch("pita_egnn_wide_vjp", p.H <= 32 ? egnn_wide_vjp_kernel<32> : egnn_wide_vjp_kernel<64>, g, q, st);
 }

@@ -60,6 +60,60 @@ struct Wide64Cfg {
   }
 };
 
+// ---- host side, shared by the three files' tables (P: the kernel's parameter block)
+// One kernel of a row, its four [attention][tanh] instantiations: an item is G walkers (forward kernel) or one walker /
+// (walker, direction) pair on item_waves waves (derivative kernels); `waves` waves per block, one block per CU
+template <class P>
+struct Wide64Kernel {
+  void (*fn[2][2])(P);
+  size_t (*lds_bytes)(int);
+  int G, waves, item_waves;
+};
+template <class P>
+struct Wide64Row {
+  int n, dim;
+  Wide64Kernel<P> k;
+  Wide64Kernel<P> alt;        // forward: the small-batch mapping (fn null: none); forward mode: (walker, direction) items
+  size_t (*ck_item_f)(int);   // reverse mode: floats of checkpoint scratch per resident item
+};
+template <class C>
+static size_t wide64_lds_of(int L) { return C::lds_bytes(L); }
+// K(ATT, TANH): a function-like macro that names one instantiation
+#define PITA_WIDE64_FNS(K) {{K(false, false), K(false, true)}, {K(true, false), K(true, true)}}
+
+// the row of the handle's particle system, when the LDS of its kernel holds the handle's depth
+template <class P, size_t K>
+static const Wide64Row<P>* wide64_find(const Wide64Row<P> (&rows)[K], const pita_egnn_wide_config& c) {
+  for (const auto& r : rows)
+    if (r.n == c.n_particles && r.dim == c.n_dim && r.k.lds_bytes(c.n_layers) <= kWideLdsBlock) return &r;
+  return nullptr;
+}
+template <class P>
+static unsigned wide64_grid(const pita_egnn_wide* net, const Wide64Kernel<P>& k, long long count) {
+  const long long items = (count + k.G - 1) / k.G, per_block = k.waves / k.item_waves;
+  const long long want = (items + per_block - 1) / per_block, cap = net->n_cu;
+  return (unsigned)(want < cap ? want : cap);
+}
+template <class P>
+static int wide64_launch(const pita_egnn_wide* net, const Wide64Kernel<P>& k, unsigned grid, const P& p, hipStream_t st) {
+  const auto fn = k.fn[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
+  const size_t lds = k.lds_bytes(net->cfg.n_layers);
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(fn), lds));
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(k.waves * 64), lds, st, p);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+// the fields the three parameter blocks share
+template <class P>
+static P wide64_params(const pita_egnn_wide* net, long long B) {
+  P p{};
+  p.m16h = net->m16h.as<unsigned>(); p.vecs = net->vecs64.as<float>(); p.est = net->est64.as<float>();
+  p.L = net->cfg.n_layers; p.has_beta = net->cfg.condition_beta;
+  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
+  p.B = B;
+  return p;
+}
+
 #ifndef PITA_WIDE64_AGPR_WEIGHTS
 #define PITA_WIDE64_AGPR_WEIGHTS 1
 #endif

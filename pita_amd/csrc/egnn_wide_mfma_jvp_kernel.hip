@@ -332,74 +332,31 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
   }
 }
 
-struct Wide64JvpShape {
-  int n, dim, waves;
-  void (*kernel[2][2])(Wide64JvpParams);  // [attention][tanh]
-  void (*multi[2][2])(Wide64JvpParams);   // the same over (walker, direction) items
-  size_t (*lds_bytes)(int);
-};
-template <int N, int DIM, int WAVES>
-static size_t wide64_jvp_lds_of(int L) { return Wide64JvpCfg<N, DIM, WAVES>::lds_bytes(L); }
-#define PITA_WIDE64_JVP_SHAPE(N, DIM, WAVES)                                                                               \
-  Wide64JvpShape { N, DIM, WAVES,                                                                                          \
-                   {{egnn_wide64_jvp_kernel<N, DIM, WAVES, false, false>, egnn_wide64_jvp_kernel<N, DIM, WAVES, false, true>}, \
-                    {egnn_wide64_jvp_kernel<N, DIM, WAVES, true, false>, egnn_wide64_jvp_kernel<N, DIM, WAVES, true, true>}},  \
-                   {{egnn_wide64_jvp_kernel<N, DIM, WAVES, false, false, true>,                                            \
-                     egnn_wide64_jvp_kernel<N, DIM, WAVES, false, true, true>},                                             \
-                    {egnn_wide64_jvp_kernel<N, DIM, WAVES, true, false, true>,                                             \
-                     egnn_wide64_jvp_kernel<N, DIM, WAVES, true, true, true>}},                                             \
-                   wide64_jvp_lds_of<N, DIM, WAVES> }
 // alanine dipeptide (22 atoms: one wave per item), tri-alanine (33) and ACE-(ALA)3-NME (42: two waves per item, one per
-// column tile); other particle counts take the vector-pipe kernel
-static const Wide64JvpShape kWide64JvpShapes[] = {PITA_WIDE64_JVP_SHAPE(22, 3, 4), PITA_WIDE64_JVP_SHAPE(33, 3, 4),
-                                                  PITA_WIDE64_JVP_SHAPE(42, 3, 4)};
-
-static const Wide64JvpShape* wide64_jvp_shape(const pita_egnn_wide* net) {
-  if (!net->shape64) return nullptr;
-  for (const auto& t : kWide64JvpShapes)
-    if (t.n == net->cfg.n_particles && t.dim == net->cfg.n_dim && t.lds_bytes(net->cfg.n_layers) <= 160 * 1024) return &t;
-  return nullptr;
+// column tile: 4 or 2 items per block); other particle counts take the vector-pipe kernel
+template <int N, int DIM, int WAVES>
+static Wide64Row<Wide64JvpParams> wide64_jvp_row_of() {
+  using C = Wide64JvpCfg<N, DIM, WAVES>;
+#define PITA_K(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T>
+#define PITA_KM(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T, true>
+  return {N, DIM, {PITA_WIDE64_FNS(PITA_K), wide64_lds_of<C>, 1, WAVES, C::NT},
+          {PITA_WIDE64_FNS(PITA_KM), wide64_lds_of<C>, 1, WAVES, C::NT}};
+#undef PITA_K
+#undef PITA_KM
 }
+static const Wide64Row<Wide64JvpParams> kWide64JvpRows[] = {wide64_jvp_row_of<22, 3, 4>(), wide64_jvp_row_of<33, 3, 4>(),
+                                                            wide64_jvp_row_of<42, 3, 4>()};
 
-int wide64_jvp_available(const pita_egnn_wide* net) { return wide64_jvp_shape(net) ? 1 : 0; }
+const Wide64Row<Wide64JvpParams>* wide64_jvp_row(const pita_egnn_wide_config& cfg) { return wide64_find(kWide64JvpRows, cfg); }
 
-// returns PITA_OK when the matrix-pipe kernel took the launch, 1 when the particle system has no instantiation;
-// multi: all n*d unit directions of every walker in one launch (vx, dir, vh, dout, dot_out unused; diag_acc: [n*d, B])
-static int wide64_jvp_launch(pita_egnn_wide* net, bool multi, const float* h, const float* x, const float* beta,
-                             const float* vx, int dir, const float* vh, float* out, float* dout, float* dot_out,
-                             long long dot_stride, long long dot_off, float* diag_acc, int* bad, long long B,
-                             hipStream_t stream) {
-  const Wide64JvpShape* s = wide64_jvp_shape(net);
-  if (!s) return 1;
-  auto kernel = (multi ? s->multi : s->kernel)[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
-  const size_t lds = s->lds_bytes(net->cfg.n_layers);
-  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
-  Wide64JvpParams p{};
-  p.m16h = net->d_m16h; p.vecs = net->d_vecs64; p.est = net->d_est64;
-  p.L = net->cfg.n_layers; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.B = B; p.x = x; p.h = h; p.beta = beta; p.vx = vx; p.vh = vh; p.dir = vx ? -1 : dir;
-  p.out = out; p.dout = dout; p.dot_out = dot_out; p.dot_stride = dot_stride; p.dot_off = dot_off; p.diag_acc = diag_acc;
-  p.bad = bad;
-  // one item per ceil(n / 32) waves (a wave per 32-column tile): 4 or 2 items per block, one 4-wave block per CU
-  const long long items = multi ? B * s->n * s->dim : B, ipb = s->waves / ((s->n + 31) / 32);
-  const long long want = (items + ipb - 1) / ipb, cap = net->n_cu;
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->waves * 64), lds, stream, p);
-  PITA_LAUNCH_CHECK();
-  return PITA_OK;
-}
-
-int wide64_jvp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* vx, int dir,
-               const float* vh, float* out, float* dout, float* dot_out, long long dot_stride, long long dot_off,
-               float* diag_acc, int* bad, long long B, hipStream_t stream) {
-  return wide64_jvp_launch(net, false, h, x, beta, vx, dir, vh, out, dout, dot_out, dot_stride, dot_off, diag_acc, bad, B,
-                           stream);
-}
-
-int wide64_jvp_multi(pita_egnn_wide* net, const float* h, const float* x, const float* beta, float* out, float* diag,
-                     int* bad, long long B, hipStream_t stream) {
-  return wide64_jvp_launch(net, true, h, x, beta, nullptr, -1, nullptr, out, nullptr, nullptr, 0, 0, diag, bad, B, stream);
+int wide64_jvp(pita_egnn_wide* net, const WideJvpParams& v, bool multi, int* bad, hipStream_t stream) {
+  Wide64JvpParams p = wide64_params<Wide64JvpParams>(net, v.base.B);
+  p.x = v.base.x; p.h = v.base.t; p.beta = v.base.beta; p.out = v.base.out;
+  p.vx = v.vx; p.vh = v.vh; p.dir = v.dir; p.dout = v.dout; p.dot_out = v.dot_out; p.dot_stride = v.dot_stride;
+  p.dot_off = v.dot_off; p.diag_acc = v.diag_acc; p.bad = bad;
+  const Wide64Kernel<Wide64JvpParams>& k = multi ? net->jvp64->alt : net->jvp64->k;
+  const long long items = multi ? p.B * net->cfg.n_particles * net->cfg.n_dim : p.B;
+  return wide64_launch(net, k, wide64_grid(net, k, items), p, stream);
 }
 
 }  // namespace pita

@@ -360,48 +360,40 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_kernel(Wide64Params
   }
 }
 
-struct Wide64Shape {
-  int n, dim, G, waves;
-  void (*kernel[2][2])(Wide64Params);  // [attention][tanh]
-  size_t (*lds_bytes)(int);
-};
 template <int N, int DIM, int G, int WAVES>
-static size_t wide64_lds_of(int L) { return Wide64Cfg<N, DIM, G, WAVES>::lds_bytes(L); }
-#define PITA_WIDE64_SHAPE(N, DIM, G, WAVES)                                                                         \
-  Wide64Shape { N, DIM, G, WAVES,                                                                                  \
-                {{egnn_wide64_kernel<N, DIM, G, WAVES, false, false>, egnn_wide64_kernel<N, DIM, G, WAVES, false, true>}, \
-                 {egnn_wide64_kernel<N, DIM, G, WAVES, true, false>, egnn_wide64_kernel<N, DIM, G, WAVES, true, true>}}, \
-                wide64_lds_of<N, DIM, G, WAVES> }
+static Wide64Kernel<Wide64Params> wide64_kernel_of() {
+#define PITA_K(A, T) egnn_wide64_kernel<N, DIM, G, WAVES, A, T>
+  return {PITA_WIDE64_FNS(PITA_K), wide64_lds_of<Wide64Cfg<N, DIM, G, WAVES>>, G, WAVES, 1};
+#undef PITA_K
+}
 // the particle counts EGNN_dynamics_AD2_cat.get_h_initial knows (egnn_dynamics_ad2_cat.py:66-92): alanine dipeptide (22
 // atoms: 4 walkers = 88 of 96 columns), tri- / tetra-alanine (33, 42 atoms: 2 walkers = 66 / 84 of 96), LJ13 (7 walkers =
-// 91 of 96), LJ55 (1 walker = 55 of 64)
-static const Wide64Shape kWide64Shapes[] = {PITA_WIDE64_SHAPE(22, 3, 4, 4), PITA_WIDE64_SHAPE(33, 3, 2, 4),
-                                            PITA_WIDE64_SHAPE(42, 3, 2, 4), PITA_WIDE64_SHAPE(13, 3, 7, 4),
-                                            PITA_WIDE64_SHAPE(55, 3, 1, 4)};
-// Fewer walkers per wave for batches that leave SIMDs empty with the mapping above (4 096 alanine-dipeptide walkers are
-// 1 024 groups of four = one wave per SIMD; below that, one walker per wave -- 22 of 32 columns -- fills the chip
+// 91 of 96), LJ55 (1 walker = 55 of 64).
+// alt: fewer walkers per wave for batches that leave SIMDs empty with the mapping above (4 096 alanine-dipeptide walkers
+// are 1 024 groups of four = one wave per SIMD; below that, one walker per wave -- 22 of 32 columns -- fills the chip
 // sooner).  Results do not depend on the grouping (columns are independent; tested bitwise).
-static const Wide64Shape kWide64Small[] = {PITA_WIDE64_SHAPE(22, 3, 1, 4)};
+static const Wide64Row<Wide64Params> kWide64Rows[] = {
+    {22, 3, wide64_kernel_of<22, 3, 4, 4>(), wide64_kernel_of<22, 3, 1, 4>()},
+    {33, 3, wide64_kernel_of<33, 3, 2, 4>()},
+    {42, 3, wide64_kernel_of<42, 3, 2, 4>()},
+    {13, 3, wide64_kernel_of<13, 3, 7, 4>()},
+    {55, 3, wide64_kernel_of<55, 3, 1, 4>()},
+};
 
 static inline int kfeat64(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
+int wide64_prepare(pita_egnn_wide* net, const WideWeights& W, const float* he) {
   const pita_egnn_wide_config& cfg = net->cfg;
-  const Wide64Shape* shape = nullptr;
-  for (const auto& s : kWide64Shapes)
-    if (s.n == cfg.n_particles && s.dim == cfg.n_dim) shape = &s;
-  if (!shape) return PITA_OK;
-  const int H = cfg.hidden_nf, L = cfg.n_layers, ns = cfg.n_static, n = cfg.n_particles;
-  const int nf = ns + 1 + (cfg.condition_beta ? 1 : 0);
-  if (shape->lds_bytes(L) > 160 * 1024) return PITA_OK;  // deeper than the LDS holds: the vector-pipe kernel serves it
-  const size_t n_m = (size_t)L * WM_COUNT * W64_MAT_W, n_v = W64_HEAD_F + (size_t)L * W64_LAYER_F;
-  unsigned* hm = new unsigned[n_m]();
-  float* hv = new float[n_v]();
-  float* hes = new float[(size_t)n * 64]();
+  net->fwd64 = wide64_find(kWide64Rows, cfg);  // null also when deeper than the LDS holds: the vector-pipe kernel serves it
+  if (!net->fwd64) return PITA_OK;
+  net->jvp64 = wide64_jvp_row(cfg);
+  net->vjp64 = wide64_vjp_row(cfg);
+  const int H = W.H, L = cfg.n_layers, ns = W.ns, nf = W.nf, n = cfg.n_particles;
+  std::vector<unsigned> hm((size_t)L * WM_COUNT * W64_MAT_W);
+  std::vector<float> hv(W64_HEAD_F + (size_t)L * W64_LAYER_F), hes((size_t)n * 64);
   // reverse-mode kernel: the unscaled transposes as bf16 x 3 fragments, unscaled w_r / w_e in fragment order
-  const size_t n_mt = (size_t)L * WM_COUNT * W64T_MAT_W, n_vt = (size_t)L * W64T_VEC_F;
-  unsigned* hmt = new unsigned[n_mt]();
-  float* hvt = new float[n_vt]();
+  std::vector<unsigned> hmt((size_t)L * WM_COUNT * W64T_MAT_W);
+  std::vector<float> hvt((size_t)L * W64T_VEC_F);
   const float kS = SILU_PRESCALE, kSi = 1.0f / SILU_PRESCALE, up = F16_SX * F16_SW, dn = 1.0f / F16_SX;
   auto f16_bits = [](float v) { _Float16 h = (_Float16)v; unsigned short u; memcpy(&u, &h, 2); return (unsigned)u; };
   // block (ob, kb) of F16_SW sc M[:, col0 : col0 + H] as a WFrag<2> fragment; rows / columns beyond H are zero
@@ -455,155 +447,71 @@ int wide64_prepare(pita_egnn_wide* net, const float* w, const float* he) {
           dst[b * 32 + hh * 16 + r] = f < H ? sc * v[(size_t)f * stride] : 0.f;
         }
   };
-  const float* q = w;
-  const float* emb_w = q; q += H * nf;
-  q += H;             // embedding bias: inside he
-  q += nf * H + nf;   // embedding_out: dead (h_final is discarded, egnn_dynamics_ad2_cat.py:187)
-  pack_vec(hv, emb_w + ns, nf, 1.0f);
-  if (cfg.condition_beta) pack_vec(hv + 64, emb_w + ns + 1, nf, 1.0f);
-  for (int i = 0; i < n; ++i) pack_vec(hes + (size_t)i * 64, he + (size_t)i * 64, 1, 1.0f);
+  pack_vec(hv.data(), W.emb_w + ns, nf, 1.0f);
+  if (cfg.condition_beta) pack_vec(hv.data() + 64, W.emb_w + ns + 1, nf, 1.0f);
+  for (int i = 0; i < n; ++i) pack_vec(hes.data() + (size_t)i * 64, he + (size_t)i * 64, 1, 1.0f);
   for (int l = 0; l < L; ++l) {
-    unsigned* ml = hm + (size_t)l * WM_COUNT * W64_MAT_W;
-    float* vl = hv + W64_HEAD_F + (size_t)l * W64_LAYER_F;
-    const float* e0w = q; q += H * (2 * H + 2);
-    const float* e0b = q; q += H;
-    const float* e2w = q; q += H * H;
-    const float* e2b = q; q += H;
-    const float* n0w = q; q += H * 2 * H;
-    const float* n0b = q; q += H;
-    const float* n2w = q; q += H * H;
-    const float* n2b = q; q += H;
-    const float* c0w = q; q += H * H;
-    const float* c0b = q; q += H;
-    const float* c2w = q; q += H;
-    const float* aw = nullptr; const float* ab = nullptr;
-    if (cfg.attention) { aw = q; q += H; ab = q; q += 1; }
+    unsigned* ml = hm.data() + (size_t)l * WM_COUNT * W64_MAT_W;
+    float* vl = hv.data() + W64_HEAD_F + (size_t)l * W64_LAYER_F;
+    const WideLayerW& v = W.layer[l];
     // SiLU pre-scale kS and the f16-path scales are folded in as pita_egnn_create does for precision 2
-    pack_mat(ml, WM_WA, e0w, 2 * H + 2, 0, kS);
-    pack_mat(ml, WM_WB, e0w, 2 * H + 2, H, kS);
-    pack_mat(ml, WM_W2, e2w, H, 0, 1.0f);
-    pack_mat(ml, WM_WC1, c0w, H, 0, 1.0f);
-    pack_mat(ml, WM_WN1A, n0w, 2 * H, 0, kS);
-    pack_mat(ml, WM_WN1B, n0w, 2 * H, H, 1.0f);
-    pack_mat(ml, WM_WN2, n2w, H, 0, kSi);
+    pack_mat(ml, WM_WA, v.e0w, 2 * H + 2, 0, kS);
+    pack_mat(ml, WM_WB, v.e0w, 2 * H + 2, H, kS);
+    pack_mat(ml, WM_W2, v.e2w, H, 0, 1.0f);
+    pack_mat(ml, WM_WC1, v.c0w, H, 0, 1.0f);
+    pack_mat(ml, WM_WN1A, v.n0w, 2 * H, 0, kS);
+    pack_mat(ml, WM_WN1B, v.n0w, 2 * H, H, 1.0f);
+    pack_mat(ml, WM_WN2, v.n2w, H, 0, kSi);
     for (int b = 0; b < 2; ++b)
       for (int o = 0; o < 32; ++o) {
         const int f = b * 32 + o;
-        vl[WV_WRE * 64 + b * 64 + o] = f < H ? kS * e0w[(size_t)f * (2 * H + 2) + 2 * H] : 0.f;
-        vl[WV_WRE * 64 + b * 64 + 32 + o] = f < H ? kS * e0w[(size_t)f * (2 * H + 2) + 2 * H + 1] : 0.f;
+        vl[WV_WRE * 64 + b * 64 + o] = f < H ? kS * v.e0w[(size_t)f * (2 * H + 2) + 2 * H] : 0.f;
+        vl[WV_WRE * 64 + b * 64 + 32 + o] = f < H ? kS * v.e0w[(size_t)f * (2 * H + 2) + 2 * H + 1] : 0.f;
       }
-    pack_vec(vl + WV_B1 * 64, e0b, 1, kS * up);
-    pack_vec(vl + WV_B2 * 64, e2b, 1, kS * up);
-    if (aw) pack_vec(vl + WV_WATT * 64, aw, 1, kSi * dn);
-    pack_vec(vl + WV_BC1 * 64, c0b, 1, kS * up);
-    pack_vec(vl + WV_WC2 * 64, c2w, 1, kSi * dn);
-    pack_vec(vl + WV_BN1 * 64, n0b, 1, kS * up);
-    pack_vec(vl + WV_BN2 * 64, n2b, 1, up);
-    vl[WV_COUNT * 64] = ab ? ab[0] : 0.f;
-    unsigned* mtl = hmt + (size_t)l * WM_COUNT * W64T_MAT_W;
-    pack_mat_t(mtl, WM_WA, e0w, 2 * H + 2, 0);
-    pack_mat_t(mtl, WM_WB, e0w, 2 * H + 2, H);
-    pack_mat_t(mtl, WM_W2, e2w, H, 0);
-    pack_mat_t(mtl, WM_WC1, c0w, H, 0);
-    pack_mat_t(mtl, WM_WN1A, n0w, 2 * H, 0);
-    pack_mat_t(mtl, WM_WN1B, n0w, 2 * H, H);
-    pack_mat_t(mtl, WM_WN2, n2w, H, 0);
-    pack_vec(hvt + (size_t)l * W64T_VEC_F, e0w + 2 * H, 2 * H + 2, 1.0f);
-    pack_vec(hvt + (size_t)l * W64T_VEC_F + 64, e0w + 2 * H + 1, 2 * H + 2, 1.0f);
+    pack_vec(vl + WV_B1 * 64, v.e0b, 1, kS * up);
+    pack_vec(vl + WV_B2 * 64, v.e2b, 1, kS * up);
+    if (v.aw) pack_vec(vl + WV_WATT * 64, v.aw, 1, kSi * dn);
+    pack_vec(vl + WV_BC1 * 64, v.c0b, 1, kS * up);
+    pack_vec(vl + WV_WC2 * 64, v.c2w, 1, kSi * dn);
+    pack_vec(vl + WV_BN1 * 64, v.n0b, 1, kS * up);
+    pack_vec(vl + WV_BN2 * 64, v.n2b, 1, up);
+    vl[WV_COUNT * 64] = v.ab ? v.ab[0] : 0.f;
+    unsigned* mtl = hmt.data() + (size_t)l * WM_COUNT * W64T_MAT_W;
+    pack_mat_t(mtl, WM_WA, v.e0w, 2 * H + 2, 0);
+    pack_mat_t(mtl, WM_WB, v.e0w, 2 * H + 2, H);
+    pack_mat_t(mtl, WM_W2, v.e2w, H, 0);
+    pack_mat_t(mtl, WM_WC1, v.c0w, H, 0);
+    pack_mat_t(mtl, WM_WN1A, v.n0w, 2 * H, 0);
+    pack_mat_t(mtl, WM_WN1B, v.n0w, 2 * H, H);
+    pack_mat_t(mtl, WM_WN2, v.n2w, H, 0);
+    pack_vec(hvt.data() + (size_t)l * W64T_VEC_F, v.e0w + 2 * H, 2 * H + 2, 1.0f);
+    pack_vec(hvt.data() + (size_t)l * W64T_VEC_F + 64, v.e0w + 2 * H + 1, 2 * H + 2, 1.0f);
   }
-  hipError_t e = hipMalloc(&net->d_m16h, n_m * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(&net->d_vecs64, n_v * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&net->d_est64, (size_t)n * 64 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&net->d_flag, sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&net->d_m16t, n_mt * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(&net->d_vecs64t, n_vt * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(net->d_m16t, hmt, n_mt * sizeof(unsigned), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(net->d_vecs64t, hvt, n_vt * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(net->d_m16h, hm, n_m * sizeof(unsigned), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(net->d_vecs64, hv, n_v * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(net->d_est64, hes, (size_t)n * 64 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = ensure_dynamic_lds(reinterpret_cast<const void*>(shape->kernel[cfg.attention ? 1 : 0][cfg.tanh ? 1 : 0]),
-                           shape->lds_bytes(L));
-  for (const auto& t : kWide64Small)
-    if (e == hipSuccess && t.n == shape->n && t.dim == shape->dim)
-      e = ensure_dynamic_lds(reinterpret_cast<const void*>(t.kernel[cfg.attention ? 1 : 0][cfg.tanh ? 1 : 0]), t.lds_bytes(L));
-  delete[] hm;
-  delete[] hv;
-  delete[] hes;
-  delete[] hmt;
-  delete[] hvt;
-  if (e != hipSuccess) {
-    wide64_release(net);
-    return fail(PITA_EHIP, "pita_egnn_wide_create: matrix-pipe weights: %s", hipGetErrorString(e));
-  }
-  net->shape64 = shape;
+  auto put = [](DeviceBuf& d, const auto& h) { return d.upload(h.data(), h.size() * sizeof(h[0])); };
+  hipError_t e = put(net->m16t, hmt);
+  if (e == hipSuccess) e = put(net->vecs64t, hvt);
+  if (e == hipSuccess) e = put(net->m16h, hm);
+  if (e == hipSuccess) e = put(net->vecs64, hv);
+  if (e == hipSuccess) e = put(net->est64, hes);
+  if (e == hipSuccess) e = net->flag.grow(sizeof(int), nullptr);
+  if (e != hipSuccess) return fail(PITA_EHIP, "pita_egnn_wide_create: matrix-pipe weights: %s", hipGetErrorString(e));
   return PITA_OK;
 }
 
-void wide64_release(pita_egnn_wide* net) {
-  (void)hipFree(net->d_m16h);
-  (void)hipFree(net->d_vecs64);
-  (void)hipFree(net->d_est64);
-  (void)hipFree(net->d_bk);
-  (void)hipFree(net->d_flag);
-  (void)hipFree(net->d_jbad);
-  (void)hipFree(net->d_m16t);
-  (void)hipFree(net->d_vecs64t);
-  (void)hipFree(net->d_vjp_ck);
-  (void)hipFree(net->d_vmark);
-  net->d_m16t = nullptr;
-  net->d_vecs64t = nullptr;
-  net->d_vjp_ck = nullptr;
-  net->vjp_ck_bytes = 0;
-  net->d_vmark = nullptr;
-  net->vmark_bytes = 0;
-  net->d_jbad = nullptr;
-  net->jbad_bytes = 0;
-  net->d_flag = nullptr;
-  net->d_bk = nullptr;
-  net->bk_bytes = 0;
-  net->d_m16h = nullptr;
-  net->d_vecs64 = nullptr;
-  net->d_est64 = nullptr;
-  net->shape64 = nullptr;
-}
-
-static int wide64_run(pita_egnn_wide* net, Wide64Params& p, hipStream_t stream);
-
-int wide64_launch(pita_egnn_wide* net, int what, const float* t, const float* x, const float* beta, float* out,
-                  long long B, hipStream_t stream) {
-  Wide64Params p{};
-  p.B = B; p.mode = what; p.x = x; p.t = t; p.beta = beta; p.out = out;
-  return wide64_run(net, p, stream);
-}
-
-int wide64_sampler(pita_egnn_wide* net, float* x, long long B, const float* step_tab, int n_steps, const float* noise,
-                   unsigned long long seed, unsigned long long walker_offset, long long step0, int remove_mean,
-                   double* stats_out, int* bad_from, hipStream_t stream) {
-  Wide64Params p{};
-  p.B = B; p.mode = 3; p.xs = x; p.step_tab = step_tab; p.n_steps = n_steps; p.noise = noise; p.seed = seed;
-  p.walker_offset = walker_offset; p.step0 = step0; p.remove_mean = remove_mean; p.stats_out = stats_out;
+int wide64_forward(pita_egnn_wide* net, const WideParams& v, int* bad_from, hipStream_t stream) {
+  Wide64Params p = wide64_params<Wide64Params>(net, v.B);
+  p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh;
+  p.mode = v.mode; p.x = v.x; p.t = v.t; p.beta = v.beta; p.out = v.out;
+  p.xs = v.xs; p.step_tab = v.step_tab; p.n_steps = v.n_steps; p.noise = v.noise; p.seed = v.seed;
+  p.walker_offset = v.walker_offset; p.step0 = v.step0; p.remove_mean = v.remove_mean; p.stats_out = v.stats_out;
   p.bad_from = bad_from;
-  return wide64_run(net, p, stream);
-}
-
-static int wide64_run(pita_egnn_wide* net, Wide64Params& p, hipStream_t stream) {
-  const long long B = p.B;
-  const Wide64Shape* s = static_cast<const Wide64Shape*>(net->shape64);
-  for (const auto& t : kWide64Small)  // small batch: the one-walker mapping when the regular one fills under 3/4 of the SIMDs
-    if (t.n == s->n && t.dim == s->dim && (B + s->G - 1) / s->G < (long long)net->n_cu * 3) s = &t;
-  p.m16h = net->d_m16h; p.vecs = net->d_vecs64; p.est = net->d_est64;
-  p.L = net->cfg.n_layers; p.attention = net->cfg.attention; p.tanh_on = net->cfg.tanh; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)net->cfg.n_layers;
-  p.flag = net->d_flag;
-  if (p.flag) PITA_HIP_CHECK(hipMemsetAsync(p.flag, 0, sizeof(int), stream));
-  const long long ngroups = (B + s->G - 1) / s->G;
-  const long long want = (ngroups + s->waves - 1) / s->waves, cap = net->n_cu;  // one 4-wave block per CU
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  hipLaunchKernelGGL(s->kernel[p.attention ? 1 : 0][p.tanh_on ? 1 : 0], dim3(grid), dim3(s->waves * 64), s->lds_bytes(p.L), stream, p);
-  PITA_LAUNCH_CHECK();
-  return PITA_OK;
+  p.flag = net->flag.as<int>();
+  PITA_HIP_CHECK(hipMemsetAsync(p.flag, 0, sizeof(int), stream));
+  const Wide64Row<Wide64Params>& r = *net->fwd64;
+  // small batch: the one-walker mapping when the regular one fills under 3/4 of the SIMDs
+  const bool small = r.alt.fn[0][0] && (v.B + r.k.G - 1) / r.k.G < (long long)net->n_cu * 3;
+  const Wide64Kernel<Wide64Params>& k = small ? r.alt : r.k;
+  return wide64_launch(net, k, wide64_grid(net, k, v.B), p, stream);
 }
 
 }  // namespace pita

@@ -548,57 +548,31 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_vjp_kernel(Wide64Vj
   }
 }
 
-struct Wide64VjpShape {
-  int n, dim, waves;
-  void (*kernel[2][2])(Wide64VjpParams);  // [attention][tanh]
-  size_t (*lds_bytes)(int);
-  size_t (*ck_item_f)(int);
-};
-template <int N, int DIM, int WAVES>
-static size_t wide64_vjp_lds_of(int L) { return Wide64VjpCfg<N, DIM, WAVES>::lds_bytes(L); }
+// alanine dipeptide (22 atoms: one wave per item), tri-alanine (33) and ACE-(ALA)3-NME (42: two waves per item: 4 or 2
+// resident items per block); other particle counts take the vector-pipe kernel
 template <int N, int DIM, int WAVES>
 static size_t wide64_vjp_ck_of(int L) { return Wide64VjpCfg<N, DIM, WAVES>::ck_item_f(L); }
-#define PITA_WIDE64_VJP_SHAPE(N, DIM, WAVES)                                                                               \
-  Wide64VjpShape { N, DIM, WAVES,                                                                                          \
-                   {{egnn_wide64_vjp_kernel<N, DIM, WAVES, false, false>, egnn_wide64_vjp_kernel<N, DIM, WAVES, false, true>}, \
-                    {egnn_wide64_vjp_kernel<N, DIM, WAVES, true, false>, egnn_wide64_vjp_kernel<N, DIM, WAVES, true, true>}},  \
-                   wide64_vjp_lds_of<N, DIM, WAVES>, wide64_vjp_ck_of<N, DIM, WAVES> }
-// The reverse-mode shape table: alanine dipeptide (22 atoms: one wave per item), tri-alanine (33) and ACE-(ALA)3-NME
-// (42: two waves per item); other particle counts take the vector-pipe kernel
-static const Wide64VjpShape kWide64VjpShapes[] = {PITA_WIDE64_VJP_SHAPE(22, 3, 4), PITA_WIDE64_VJP_SHAPE(33, 3, 4),
-                                                  PITA_WIDE64_VJP_SHAPE(42, 3, 4)};
-
-static const Wide64VjpShape* wide64_vjp_shape(const pita_egnn_wide* net) {
-  if (!net->shape64 || !net->d_m16t) return nullptr;
-  for (const auto& t : kWide64VjpShapes)
-    if (t.n == net->cfg.n_particles && t.dim == net->cfg.n_dim && t.lds_bytes(net->cfg.n_layers) <= 160 * 1024) return &t;
-  return nullptr;
+template <int N, int DIM, int WAVES>
+static Wide64Row<Wide64VjpParams> wide64_vjp_row_of() {
+  using C = Wide64VjpCfg<N, DIM, WAVES>;
+#define PITA_K(A, T) egnn_wide64_vjp_kernel<N, DIM, WAVES, A, T>
+  return {N, DIM, {PITA_WIDE64_FNS(PITA_K), wide64_lds_of<C>, 1, WAVES, C::NT}, {}, wide64_vjp_ck_of<N, DIM, WAVES>};
+#undef PITA_K
 }
+static const Wide64Row<Wide64VjpParams> kWide64VjpRows[] = {wide64_vjp_row_of<22, 3, 4>(), wide64_vjp_row_of<33, 3, 4>(),
+                                                            wide64_vjp_row_of<42, 3, 4>()};
 
-int wide64_vjp_available(const pita_egnn_wide* net) { return wide64_vjp_shape(net) ? 1 : 0; }
+const Wide64Row<Wide64VjpParams>* wide64_vjp_row(const pita_egnn_wide_config& cfg) { return wide64_find(kWide64VjpRows, cfg); }
 
-int wide64_vjp(pita_egnn_wide* net, const float* h, const float* x, const float* beta, const float* cot, float* out,
-               float* vjp, float* dot_h, int* mark, int* flag, long long B, hipStream_t stream) {
-  const Wide64VjpShape* s = wide64_vjp_shape(net);
-  if (!s) return 1;
-  auto kernel = s->kernel[net->cfg.attention ? 1 : 0][net->cfg.tanh ? 1 : 0];
-  const int L = net->cfg.n_layers;
-  const size_t lds = s->lds_bytes(L);
-  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
-  // one item per ceil(n / 32) waves: 4 or 2 resident items per block, one 4-wave block per CU
-  const long long ipb = s->waves / ((s->n + 31) / 32);
-  const long long want = (B + ipb - 1) / ipb, cap = net->n_cu;
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  PITA_HIP_CHECK(grow_scratch(net->d_vjp_ck, net->vjp_ck_bytes, sizeof(float) * (size_t)grid * ipb * s->ck_item_f(L), stream));
-  Wide64VjpParams p{};
-  p.m16h = net->d_m16h; p.m16t = net->d_m16t; p.vecs = net->d_vecs64; p.vecst = net->d_vecs64t; p.est = net->d_est64;
-  p.L = L; p.has_beta = net->cfg.condition_beta;
-  p.coord_scale = net->cfg.coords_range / (float)L;
-  p.B = B; p.x = x; p.h = h; p.beta = beta; p.cot = cot; p.out = out; p.vjp = vjp; p.dot_h = dot_h;
-  p.ws = net->d_vjp_ck; p.mark = mark; p.flag = flag;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->waves * 64), lds, stream, p);
-  PITA_LAUNCH_CHECK();
-  return PITA_OK;
+int wide64_vjp(pita_egnn_wide* net, const WideVjpParams& v, int* mark, int* flag, hipStream_t stream) {
+  const Wide64Row<Wide64VjpParams>& r = *net->vjp64;
+  Wide64VjpParams p = wide64_params<Wide64VjpParams>(net, v.base.B);
+  const unsigned grid = wide64_grid(net, r.k, p.B);
+  PITA_HIP_CHECK(net->vjp_ck.grow(sizeof(float) * (size_t)grid * (r.k.waves / r.k.item_waves) * r.ck_item_f(p.L), stream));
+  p.m16t = net->m16t.as<unsigned>(); p.vecst = net->vecs64t.as<float>();
+  p.x = v.base.x; p.h = v.base.t; p.beta = v.base.beta; p.cot = v.cot; p.out = v.base.out; p.vjp = v.vjp; p.dot_h = v.dot_h;
+  p.ws = net->vjp_ck.as<float>(); p.mark = mark; p.flag = flag;
+  return wide64_launch(net, r.k, grid, p, stream);
 }
 
 }  // namespace pita
