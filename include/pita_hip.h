@@ -196,6 +196,21 @@ int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, co
                        const float* cot /*nullable*/, float* out /*nullable*/, float* vjp, float* dot_h /*nullable*/,
                        int64_t B, void* stream);
 
+/* pita_egnn_wide_vjp (which forwards here with dot_parts = NULL) with the split of dot_h that pita_egnn_vjp offers:
+ * dot_parts (nullable, device [B, 2], needs dot_h): the same derivative split the way the reference's energy is written
+ * (energy_net.py:33-41, E = |x|^2 (1 - c_s)/(2h) - c_out/(c_in h) <F, c_in x>):
+ *   dot_parts[b][0] = c_out <cot, F>,   dot_parts[b][1] = <cot, d(c_out F)/dh> = dot_h[b] - c_s'(h) <cot, x>.
+ * pita_fk_assemble builds E_theta and dE_theta/dh (sdes.py:218) from these without the |x|^2/h^2-sized cancellation that
+ * the forms through <D, x> and <x, dD/dh> carry at small h.  Both kernels add the three shares over the walker in a fixed
+ * order (no atomics); a walker the matrix-pipe kernel marks gets dot_parts, like out, vjp and dot_h, from the vector-pipe
+ * kernel.  dot_parts == NULL: out, vjp and dot_h have the bits of pita_egnn_wide_vjp.  dot_parts != NULL: out and vjp keep
+ * those bits; dot_h[b] is the fp32 sum dot_parts[b][1] + (the kernel's own c_s'(h) <cot, x>), which may differ from the
+ * plain call's dot_h by rounding.  dot_parts without dot_h, or a null net, is PITA_EINVAL before any device call; B = 0
+ * is PITA_OK and touches nothing. */
+int pita_egnn_wide_vjp_parts(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta /*nullable*/,
+                             const float* cot /*nullable*/, float* out /*nullable*/, float* vjp, float* dot_h /*nullable*/,
+                             float* dot_parts /*nullable [B,2], needs dot_h*/, int64_t B, void* stream);
+
 /* trace(J_x D)(h, x) of the EDM denoiser around the wide backbone and, optionally, D itself: ONE call
  * (replaces n*d pita_egnn_wide_jvp launches, utils.py:30-51); bit-identical to them.  One launch whose work items are
  * (walker, unit direction) pairs -- the matrix-pipe kernel where pita_egnn_wide_jvp_uses_matrix_pipe (22, 33, 42

@@ -97,6 +97,7 @@ _PROTOS = {
     "pita_egnn_wide_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "pita_egnn_wide_vjp": (c_int, [c_void_p] * 8 + [c_int64, c_void_p]),
+    "pita_egnn_wide_vjp_parts": (c_int, [c_void_p] * 9 + [c_int64, c_void_p]),
     "pita_egnn_wide_jacobian_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                               c_void_p]),
     "pita_egnn_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

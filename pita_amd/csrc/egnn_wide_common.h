@@ -100,6 +100,8 @@ struct WideVjpParams {
   const float* cot;  // nullable [B, n*dim]: cotangent (null: x)
   float* vjp;        // [B, n*dim]
   float* dot_h;      // nullable [B]
+  float* dot_parts;  // nullable [B, 2] (needs dot_h): { c_out <cot, F>,  <cot, d(c_out F)/dh> = dot_h - c_s'(h) <cot, x> }
+                     // as pita_egnn_vjp defines it; then dot_h = dot_parts[1] + c_s'(h) <cot, x>, added in fp32
   float* ws;         // checkpoints: [wave slot][L][2 n 64 + n 4]
   // repair mode behind the matrix-pipe kernel (egnn_wide_mfma_vjp_kernel.hip); mark null: every walker, as ever
   const int* mark;   // nullable [B]: compute and write only the walkers marked 1

@@ -648,6 +648,7 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
   const size_t ck_layer = wide_vjp_ck_layer(n);
   float* ws = q.ws + (size_t)(blockIdx.x * waves + wave) * p.L * ck_layer;
   const bool want_h = q.dot_h != nullptr;
+  const bool want_p = q.dot_parts != nullptr;  // wave-uniform: without it the h-sum is accumulated exactly as ever
   const long long nw = (long long)gridDim.x * waves;
   if (q.mark && *q.flag == 0) return;  // nothing to repair
   for (long long w = (long long)blockIdx.x * waves + wave; w < p.B; w += nw) {
@@ -742,18 +743,28 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
       mean[k] = s / (float)n;
       cmean[k] = sc / (float)n;
     }
-    float hpart = 0.f;  // this lane's share of <cot, dD/dh>
+    // hpart: this lane's share of <cot, dD/dh>; with dot_parts, of <cot, d(c_out F)/dh> alone, beside the shares of
+    // c_out <cot, F> and c_s'(h) <cot, x>, which are summed over the wave at once (sum_f, sum_x: wave-uniform)
+    float hpart = 0.f, fpart = 0.f, xpart = 0.f;
     for (int qd = lane; qd < n * DIM; qd += 64) {
       const int i = qd / DIM, k = qd - i * DIM;
       const float F = (pos[i * 4 + k] - pos0[i * 4 + k]) - mean[k];
       const float xc = p.x[w * n * DIM + qd];
       const float ct = q.cot ? q.cot[w * n * DIM + qd] : xc;
       if (p.out) p.out[w * n * DIM + qd] = fmaf(c_s, xc, c_out * F);
-      hpart = fmaf(ct, fmaf(dc_s, xc, dc_out * F), hpart);
+      if (want_p) {
+        hpart = fmaf(ct, dc_out * F, hpart);
+        fpart = fmaf(ct, c_out * F, fpart);
+        xpart = fmaf(ct, dc_s * xc, xpart);
+      } else {
+        hpart = fmaf(ct, fmaf(dc_s, xc, dc_out * F), hpart);
+      }
       const float u = c_out * (ct - cmean[k]);
       pb[i * 4 + k] = u;
       p0b[i * 4 + k] = -u;
     }
+    float sum_f = 0.f, sum_x = 0.f;
+    if (want_p) { sum_f = wwave_sum(fpart); sum_x = wwave_sum(xpart); }
     wfence();
     // ------------------------------------------------------------------ backward sweep
     for (int l = p.L - 1; l >= 0; --l) {
@@ -877,7 +888,10 @@ __global__ void __launch_bounds__(256, 1) egnn_wide_vjp_kernel(WideVjpParams q) 
       float tb = 0.f;  // through the time feature ln(h)/8 of every node's embedding
       for (int i = 0; i < n; ++i) tb = fmaf(hb[i * WIDE_HP + lane], et, tb);
       const float s = wwave_sum(fmaf(tb, 0.125f / hval, hpart));
-      if (lane == 0) q.dot_h[w] = s;
+      if (lane == 0) {
+        q.dot_h[w] = want_p ? s + sum_x : s;
+        if (want_p) { q.dot_parts[2 * w] = sum_f; q.dot_parts[2 * w + 1] = s; }
+      }
     }
     wfence();
   }
@@ -1161,12 +1175,23 @@ extern "C" int pita_egnn_wide_sampler_run(pita_egnn_wide_t* net, float* x, int64
                      p, st);
 }
 
+// pita_egnn_wide_vjp_parts without the split
+extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta, const float* cot,
+                                  float* out, float* vjp, float* dot_h, int64_t B, void* stream) {
+  return pita_egnn_wide_vjp_parts(net, h, x, beta, cot, out, vjp, dot_h, nullptr, B, stream);
+}
+
 // Reverse-mode derivative of the denoiser around the wide backbone; arguments as pita_egnn_vjp.  Matrix-pipe kernel first
 // where pita_egnn_wide_vjp_uses_matrix_pipe (egnn_wide64_vjp_kernel); it marks the walkers whose primal left the f16 range
 // and the vector-pipe kernel (egnn_wide_vjp_kernel) then computes exactly those; the vector-pipe kernel alone otherwise.
-extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta, const float* cot,
-                                  float* out, float* vjp, float* dot_h, int64_t B, void* stream) {
+// dot_parts (nullable): the split of dot_h that pita_fk_assemble builds E and dE/dh from without the 1/h^2 cancellation,
+// { c_out <cot, F>, <cot, d(c_out F)/dh> } as pita_egnn_vjp defines it.  Both kernels add up the shares in a fixed order;
+// a marked walker gets its dot_parts, like everything else, from the vector-pipe kernel.
+extern "C" int pita_egnn_wide_vjp_parts(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta,
+                                        const float* cot, float* out, float* vjp, float* dot_h, float* dot_parts, int64_t B,
+                                        void* stream) {
   PITA_REQUIRE(net && B >= 0, "pita_egnn_wide_vjp: bad argument");
+  PITA_REQUIRE(dot_h || !dot_parts, "pita_egnn_wide_vjp: dot_parts needs dot_h");
   if (B == 0) return PITA_OK;
   PITA_REQUIRE(h && x && vjp, "pita_egnn_wide_vjp: null argument");
   PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_vjp: beta required (condition_beta)");
@@ -1176,7 +1201,7 @@ extern "C" int pita_egnn_wide_vjp(pita_egnn_wide_t* net, const float* h, const f
   WideParams& p = q.base;
   p = wide_params(net, B, 1);
   p.x = x; p.t = h; p.beta = beta; p.out = out;
-  q.cot = cot; q.vjp = vjp; q.dot_h = dot_h;
+  q.cot = cot; q.vjp = vjp; q.dot_h = dot_h; q.dot_parts = dot_parts;
   if (wide_plan(net).vjp) {
     const size_t need = sizeof(int) * (size_t)B;
     PITA_HIP_CHECK(net->vmark.grow(need, st, sizeof(int)));

@@ -48,6 +48,7 @@ struct Wide64VjpParams {
   float* out;        // nullable: D
   float* vjp;        // [B, N*DIM]
   float* dot_h;      // nullable [B]
+  float* dot_parts;  // nullable [B, 2] (needs dot_h), see WideVjpParams
   float* ws;         // checkpoints, one region per resident item slot
   int* mark;         // [B] zeroed by the launch wrapper: 1 = left to the vector-pipe kernel
   int* flag;         // one word, zeroed by the launch wrapper: 1 = some walker is marked
@@ -126,6 +127,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_vjp_kernel(Wide64Vj
   const bool valid = col < N;
   const int live = valid ? 1 : 0;
   const bool want_h = p.dot_h != nullptr;
+  const bool want_p = p.dot_parts != nullptr;  // wave-uniform: without it the h-sum is accumulated exactly as ever
 
   // this item slot's checkpoints: [L][CK_Q][NT * 64 lanes] f32x4, then [L][NCOLP][4] positions, then the parked values
   // (addressed as checkpoint layer L: [PARK_Q][NT * 64 lanes] f32x4 behind the positions)
@@ -308,20 +310,29 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_vjp_kernel(Wide64Vj
       if (hh == 0) { red[col * 4 + k] = F[k]; pbn[col * DIM + k] = ct[k]; }
     }
     item_fence<NT>();
-    float Dv[DIM], u[DIM], hpart = 0.f;  // hpart: this column's share of <cot, dD/dh>
+    // hpart: this column's share of <cot, dD/dh>; with dot_parts, of <cot, d(c_out F)/dh> alone, and the shares of
+    // c_out <cot, F> and c_s'(h) <cot, x> (fpart, xpart) wait in the free slots 2 and 3 of `red` for the final reduction
+    float Dv[DIM], u[DIM], hpart = 0.f, fpart = 0.f, xpart = 0.f;
 #pragma unroll
     for (int k = 0; k < DIM; ++k) {
       float s = 0.f, sc = 0.f;
       for (int q = 0; q < N; ++q) { s += red[q * 4 + k]; sc += pbn[q * DIM + k]; }
       F[k] -= s / (float)N;
       Dv[k] = fmaf(c_s, xin[k], c_out * F[k]);
-      hpart = fmaf(ct[k], fmaf(dc_s, xin[k], dc_out * F[k]), hpart);
+      if (want_p) {
+        hpart = fmaf(ct[k], dc_out * F[k], hpart);
+        fpart = fmaf(ct[k], c_out * F[k], fpart);
+        xpart = fmaf(ct[k], dc_s * xin[k], xpart);
+      } else {
+        hpart = fmaf(ct[k], fmaf(dc_s, xin[k], dc_out * F[k]), hpart);
+      }
       u[k] = valid ? c_out * (ct[k] - sc / (float)N) : 0.f;
     }
     item_fence<NT>();
 #pragma unroll
     for (int k = 0; k < DIM; ++k)
       if (hh == 0) { pb[col * DIM + k] = u[k]; p0b[col * DIM + k] = -u[k]; }
+    if (want_p && hh == 0) { red[col * 4 + 2] = valid ? fpart : 0.f; red[col * 4 + 3] = valid ? xpart : 0.f; }
     f32x16 hb[2] = {zero16, zero16};  // adjoint of the node's features leaving the layer (then: entering it)
     item_fence<NT>();
 
@@ -527,11 +538,14 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_vjp_kernel(Wide64Vj
       const f32x16 et0 = lds_vec16(lds + hh * 16), et1 = lds_vec16(lds + 32 + hh * 16);
       hpart = fmaf(xhalf_sum(dot16(hb[0], et0) + dot16(hb[1], et1)), 0.125f / hv, hpart);
       ok = ok && __builtin_isfinite(hpart);
+      if (want_p) ok = ok && __builtin_isfinite(red[col * 4 + 2]) && __builtin_isfinite(red[col * 4 + 3]);
     }
     if (hh == 0) { red[col * 4] = valid ? hpart : 0.f; red[col * 4 + 1] = (valid && !ok) ? 1.0f : 0.0f; }
     item_fence<NT>();
-    float dot = 0.f, nbad = 0.f;
+    float dot = 0.f, nbad = 0.f, dot_f = 0.f, dot_x = 0.f;
     for (int q = 0; q < N; ++q) { dot += red[q * 4]; nbad += red[q * 4 + 1]; }
+    if (want_p)
+      for (int q = 0; q < N; ++q) { dot_f += red[q * 4 + 2]; dot_x += red[q * 4 + 3]; }
     if (!active) {  // a slot past the last walker: its recomputed copy writes nothing
     } else if (nbad != 0.f) {  // uniform over the item's waves: all read the same flags
       if (lane == 0 && tile == 0) { p.mark[w] = 1; *p.flag = 1; }
@@ -542,7 +556,10 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_vjp_kernel(Wide64Vj
         if (p.out) p.out[e] = Dv[k];
         p.vjp[e] = vj[k];
       }
-      if (want_h && col == 0) p.dot_h[w] = dot;
+      if (want_h && col == 0) {
+        p.dot_h[w] = want_p ? dot + dot_x : dot;
+        if (want_p) { p.dot_parts[2 * w] = dot_f; p.dot_parts[2 * w + 1] = dot; }
+      }
     }
     item_fence<NT>();
   }
@@ -571,6 +588,7 @@ int wide64_vjp(pita_egnn_wide* net, const WideVjpParams& v, int* mark, int* flag
   PITA_HIP_CHECK(net->vjp_ck.grow(sizeof(float) * (size_t)grid * (r.k.waves / r.k.item_waves) * r.ck_item_f(p.L), stream));
   p.m16t = net->m16t.as<unsigned>(); p.vecst = net->vecs64t.as<float>();
   p.x = v.base.x; p.h = v.base.t; p.beta = v.base.beta; p.cot = v.cot; p.out = v.base.out; p.vjp = v.vjp; p.dot_h = v.dot_h;
+  p.dot_parts = v.dot_parts;
   p.ws = net->vjp_ck.as<float>(); p.mark = mark; p.flag = flag;
   return wide64_launch(net, r.k, grid, p, stream);
 }

@@ -208,10 +208,17 @@ class EGNN_dynamics_AD2_cat(nn.Module):
                                                             _lib.stream_ptr(x_t.device)), "pita_egnn_wide_jacobian_trace")
         return trace, den
 
-    def vjp(self, h_t, x_t, beta, cot=None, want_primal=True, want_dot_h=False):
+    vjp_h_parts = True  # vjp(..., want_h_parts=True) is available
+
+    def vjp(self, h_t, x_t, beta, cot=None, want_primal=True, want_dot_h=False, want_h_parts=False):
         """(D, J_x D^T cot[, <cot, dD/dh>]): the EDM denoiser around this backbone and its reverse-mode derivative for a
-        per-walker cotangent (default: x_t itself) from ONE launch (pita_egnn_wide_vjp) -- same contract as
-        ``EGNN_dynamics.vjp``; ``EnergyNet.forward`` and the debiased drift use it instead of dim + 1 ``jvp`` launches."""
+        per-walker cotangent (default: x_t itself) from ONE launch (pita_egnn_wide_vjp_parts) -- same contract as
+        ``EGNN_dynamics.vjp``; ``EnergyNet.forward`` and the debiased drift use it instead of dim + 1 ``jvp`` launches.
+        ``want_h_parts`` (with want_dot_h): also [B, 2] = (c_out <cot, F>, <cot, d(c_out F)/dh>), the split of the same
+        derivative that pita_fk_assemble turns into E_theta and dE_theta/dh without cancellation at small h
+        -> (D, vjp, dot_h, parts)."""
+        if want_h_parts and not want_dot_h:
+            raise ValueError("want_h_parts needs want_dot_h")
         x_t = _lib.dev_tensor(x_t, "x_t")
         B = x_t.shape[0]
         h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
@@ -225,7 +232,11 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         out = torch.empty_like(x_t) if want_primal else None
         vjp = torch.empty_like(x_t)
         dot_h = torch.empty(B, device=x_t.device) if want_dot_h else None
-        _lib.check(_lib.lib().pita_egnn_wide_vjp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                                 _lib.ptr(cot), _lib.ptr(out), vjp.data_ptr(), _lib.ptr(dot_h), B,
-                                                 _lib.stream_ptr(x_t.device)), "pita_egnn_wide_vjp")
+        parts = torch.empty(B, 2, device=x_t.device) if want_h_parts else None
+        _lib.check(_lib.lib().pita_egnn_wide_vjp_parts(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
+                                                       _lib.ptr(cot), _lib.ptr(out), vjp.data_ptr(), _lib.ptr(dot_h),
+                                                       _lib.ptr(parts), B, _lib.stream_ptr(x_t.device)),
+                   "pita_egnn_wide_vjp_parts")
+        if want_h_parts:
+            return out, vjp, dot_h, parts
         return (out, vjp, dot_h) if want_dot_h else (out, vjp)
