@@ -221,6 +221,35 @@ int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float* h, const f
                                   const float* beta /*nullable*/, float* trace /*[B]*/,
                                   float* denoiser_out /*nullable [B, n*d]*/, int64_t B, void* stream);
 
+/* Hutchinson estimate of trace(J_x D)(h, x) from n_probes = K probes and, optionally, D itself: ONE call (the
+ * estimator the reference's utils.py ships beside compute_divergence_exact, :30-51; what VEReverseSDE's cdf= slot is
+ * for).  estimate[b] = (sum_k q[k, b], added in probe order from +0) / (float)K with q[k, b] = <v_k, J_x D v_k>;
+ * per_probe (nullable) receives q.  One launch whose work items are (walker, probe) pairs, each computed exactly as
+ * pita_egnn_wide_jvp(vx = v_k, vh = NULL) computes its tangent -- the matrix-pipe kernel where
+ * pita_egnn_wide_jvp_uses_matrix_pipe, the vector-pipe kernel on exactly the items it flagged (and on all items of every
+ * other shape, or under PITA_WIDE_NO_MFMA) -- writes q to a handle-owned scratch; no atomics, every sum in a fixed
+ * order, so a walker's bits depend on neither B nor its row.  denoiser_out has the bits of
+ * pita_egnn_wide_jacobian_trace's.
+ * probes != NULL: v_k = probes[k, b, :], arbitrary floats (parity hook).  probes == NULL: Rademacher signs from the
+ * library's Philox4x32-10 keyed (seed, walker_offset + b, step) like the samplers' noise, counter tag
+ * 0x80000 | (k << 10) | particle (disjoint from the noise tags, particle < 1 024, and from the MALA uniform's 0xFFFFF);
+ * coordinate c of the particle is +1 where bit c of the first output word is set, else -1: what pita_rademacher_probes
+ * writes out for the same key.  The drawn path needs K <= 256 and n_particles <= 1 023.
+ * The estimate is unbiased with variance (1 / 2K) sum_{i != j} (J_ij + J_ji)^2 per walker.
+ * B = 0 is PITA_OK and touches nothing; a null net / h / x / estimate, n_probes < 1, K > 256 on the drawn path or a
+ * missing beta on a condition_beta handle is PITA_EINVAL before any device call. */
+int pita_egnn_wide_trace_probes(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta /*nullable*/,
+                                int n_probes, const float* probes /*nullable [K,B,n*d]*/, uint64_t seed,
+                                uint64_t walker_offset, int64_t step, float* estimate /*[B]*/,
+                                float* per_probe /*nullable [K,B]*/, float* denoiser_out /*nullable [B,n*d]*/,
+                                int64_t B, void* stream);
+/* The Rademacher probes (+1 / -1) that pita_egnn_wide_trace_probes draws in its kernels for (seed, walker_offset, step),
+ * from the same device function: out[k, b, :] is probe k of walker walker_offset + b, so the drawn path can be replayed
+ * through the injected one, and backbones without a probe kernel draw theirs here.  1 <= n_probes <= 256,
+ * 1 <= n_particles <= 1 023, 1 <= n_dim <= 32; B = 0 is PITA_OK and touches nothing. */
+int pita_rademacher_probes(float* out /*[K,B,n*d]*/, int64_t B, int n_particles, int n_dim, int n_probes, uint64_t seed,
+                           uint64_t walker_offset, int64_t step, void* stream);
+
 /* Diagonal Gaussian mixture with equal weights.
  * replaces GMM.__call__ (pita/src/energies/gmm_energy.py:87-90) ->
  * fab GMM.log_prob (fab/fab/target_distributions/gmm.py:71-79,104).

@@ -100,6 +100,9 @@ _PROTOS = {
     "pita_egnn_wide_vjp_parts": (c_int, [c_void_p] * 9 + [c_int64, c_void_p]),
     "pita_egnn_wide_jacobian_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                               c_void_p]),
+    "pita_egnn_wide_trace_probes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_uint64,
+                                            c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pita_rademacher_probes": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_uint64, c_uint64, c_int64, c_void_p]),
     "pita_egnn_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pita_egnn_edm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pita_egnn_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -184,6 +184,23 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t walker, 
   return ((c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
 
+// Rademacher signs of one particle's coordinates in Hutchinson probe `probe` (the estimator beside
+// compute_divergence_exact in the reference's utils.py): keyed (seed, walker, step) like the normals above, counter tag
+// 0x80000 | (probe << 10) | particle in c3; coordinate k of the particle is +1 where bit k of the FIRST output word is set,
+// -1 where it is clear (rademacher_sign).  The tag is disjoint from the normals' (particle < 1 024 there) and from the MALA
+// uniform's 0xFFFFF under the same key, stays below the step's high bits (bit 20 up) for probe < 256 and particle < 1 024
+// -- the callers refuse anything larger --, and depends on neither the batch size nor the walker's place in it.  The ONE
+// draw behind pita_rademacher_probes and the probe items of the wide forward-mode kernels.
+constexpr int kMaxDrawnProbes = 256, kMaxProbeParticles = 1023;
+__device__ __forceinline__ uint32_t philox_rademacher_word(uint64_t seed, uint64_t walker, int64_t step, uint32_t probe,
+                                                           uint32_t particle) {
+  uint32_t c[4] = {(uint32_t)walker, (uint32_t)(walker >> 32), (uint32_t)step,
+                   (0x80000u | (probe << 10) | particle) ^ ((uint32_t)((uint64_t)step >> 32) << 20)};
+  Philox::gen(c, seed);
+  return c[0];
+}
+__device__ __forceinline__ float rademacher_sign(uint32_t word, int k) { return ((word >> k) & 1u) ? 1.0f : -1.0f; }
+
 }  // namespace pita
 
 // makes `device` current for the lifetime of the guard (no-op when it already is)

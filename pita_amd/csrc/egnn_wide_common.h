@@ -94,7 +94,17 @@ struct WideJvpParams {
   float* diag_acc;       // nullable: diag_acc[b] += dD[b, dir]; MULTI: [n*dim, B], diag_acc[dir * B + b] = dD[b, dir]
   const int* only_bad;   // nullable [B] (MULTI: [B * n*dim], one per item): process only what the matrix-pipe kernel
                          // flagged (egnn_wide_mfma_jvp_kernel.hip)
+  // (walker, probe) items (pita_egnn_wide_trace_probes): item = walker * n_probes + probe, tangent input v_probe,
+  // diag_acc[probe * B + walker] = <v_probe, dD>, only_bad one per item
+  int n_probes;
+  const float* probes;   // nullable [n_probes, B, n*dim]; null: Rademacher signs drawn in the kernel (common.h:
+                         // philox_rademacher_word keyed seed, walker_offset + walker, step)
+  unsigned long long seed, walker_offset;
+  long long step;
 };
+// the kinds of work item of the two forward-mode kernels
+enum { WIDE_JVP_ONE = 0 /* walker, one direction per launch */, WIDE_JVP_UNIT /* (walker, unit direction) */,
+       WIDE_JVP_PROBE /* (walker, probe) */ };
 struct WideVjpParams {
   WideParams base;   // x, t (= h), beta, out (nullable: the denoiser)
   const float* cot;  // nullable [B, n*dim]: cotangent (null: x)
@@ -139,8 +149,10 @@ struct pita_egnn_wide {
   // scratch, grown on demand
   pita::DeviceBuf bk;       // fused sampler: backup of the walkers + per-particle bookkeeping for the repair pass
   pita::DeviceBuf jbad;     // int [B] marks of the forward-mode kernel (walkers left to the vector-pipe kernel);
-                            // [B * n*d], one per (walker, direction) item, in pita_egnn_wide_jacobian_trace
-  pita::DeviceBuf jdiag;    // pita_egnn_wide_jacobian_trace: [n*d, B] diagonal entries dD[b, dir] before the reduction
+                            // [B * n*d], one per (walker, direction) item, in pita_egnn_wide_jacobian_trace; [B * K], one
+                            // per (walker, probe) item, in pita_egnn_wide_trace_probes
+  pita::DeviceBuf jdiag;    // pita_egnn_wide_jacobian_trace: [n*d, B] diagonal entries dD[b, dir] before the reduction;
+                            // pita_egnn_wide_trace_probes: [K, B] quadratic forms <v_k, dD> before the mean
   pita::DeviceBuf vjp_ws;   // reverse mode, vector pipe: per-wave checkpoints of the forward sweep
   pita::DeviceBuf vjp_ck;   // reverse mode, matrix pipe: the same, one region per resident item slot
   pita::DeviceBuf vmark;    // int [B] walkers the reverse-mode kernel left to the vector pipe; one flag word behind them
@@ -167,9 +179,10 @@ const Wide64Row<Wide64VjpParams>* wide64_vjp_row(const pita_egnn_wide_config& cf
 // its vector-pipe sibling takes.
 // evaluation modes 0-2 and the fused sampler (mode 3: bad_from device [B * n]); zeroes and passes net->flag
 int wide64_forward(pita_egnn_wide* net, const WideParams& v, int* bad_from, hipStream_t stream);
-// forward-mode derivative; multi: all B * n*d (walker, unit direction) items in one launch, diag_acc[dir * B + b];
-// bad: device [B] ([B * n*d]) ints, zeroed by the caller, set to 1 for what is left to the vector-pipe kernel
-int wide64_jvp(pita_egnn_wide* net, const WideJvpParams& v, bool multi, int* bad, hipStream_t stream);
+// forward-mode derivative; kind WIDE_JVP_UNIT: all B * n*d (walker, unit direction) items in one launch, diag_acc[dir * B +
+// b]; WIDE_JVP_PROBE: all B * n_probes (walker, probe) items, diag_acc[probe * B + b]; bad: device ints, one per item,
+// zeroed by the caller, set to 1 for what is left to the vector-pipe kernel
+int wide64_jvp(pita_egnn_wide* net, const WideJvpParams& v, int kind, int* bad, hipStream_t stream);
 // reverse-mode sweep; mark: device [B] ints and flag: one int, zeroed by the caller: set to 1 for the walkers left to the
 // vector-pipe kernel / when there is one
 int wide64_vjp(pita_egnn_wide* net, const WideVjpParams& v, int* mark, int* flag, hipStream_t stream);

@@ -417,8 +417,13 @@ __device__ __forceinline__ void dense_mem2(const float* __restrict__ wt, float* 
 // MULTI: the work items are (walker, unit direction) pairs, item = walker * n*dim + direction, each computed exactly as
 // the single-direction launch with vx = vh = null computes it; the item's diagonal entry goes to its own slot (plain
 // store), the item of direction 0 writes the denoiser row; vx, vh, dir, dout and dot_out are ignored.
-template <int HK, bool MULTI = false>
+// PROBE: the work items are (walker, probe) pairs, item = walker * n_probes + probe, each computed exactly as the
+// single-direction launch with vx = v_probe, vh = null computes it (v_probe: row [probe, walker] of `probes`, or the
+// Rademacher signs of common.h's philox_rademacher_word); the item's <v_probe, dD>, summed on the path of dot_out's
+// <x, dD>, goes to its own slot diag_acc[probe * B + walker] (plain store), the item of probe 0 writes the denoiser row.
+template <int HK, int KIND = WIDE_JVP_ONE>
 __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
+  constexpr bool MULTI = KIND == WIDE_JVP_UNIT, PROBE = KIND == WIDE_JVP_PROBE;
   const WideParams& p = q.base;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -438,15 +443,26 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
   float* bc = dposn + n * 4;             // [2][64] broadcast slots (primal, tangent) of the dense layers
   const long long nw = (long long)gridDim.x * waves;
   const int ndir = n * DIM;
-  const long long items = MULTI ? p.B * ndir : p.B;
+  const long long items = MULTI ? p.B * ndir : PROBE ? p.B * q.n_probes : p.B;
   for (long long item = (long long)blockIdx.x * waves + wave; item < items; item += nw) {
     if (q.only_bad && q.only_bad[item] == 0) continue;  // wave-uniform
-    const long long w = MULTI ? item / ndir : item;
-    const int dir = MULTI ? (int)(item - w * ndir) : q.dir;
-    const float* const vxp = MULTI ? nullptr : q.vx;
+    const long long w = MULTI ? item / ndir : PROBE ? item / q.n_probes : item;
+    const int dir = MULTI ? (int)(item - w * ndir) : PROBE ? -1 : q.dir;
+    const int probe = PROBE ? (int)(item - w * q.n_probes) : 0;
+    const float* const vxp = MULTI ? nullptr : PROBE ? (q.probes ? q.probes + (long long)probe * p.B * ndir : nullptr) : q.vx;
+    // the tangent input at flat coordinate qd = (particle i, coordinate k) of the walker
+    auto dx_at = [&](int qd, int i, int k) -> float {
+      if constexpr (PROBE) {
+        if (vxp) return vxp[w * n * DIM + qd];
+        return rademacher_sign(philox_rademacher_word(q.seed, q.walker_offset + (unsigned long long)w, q.step, (uint32_t)probe,
+                                                      (uint32_t)i), k);
+      } else {
+        return vxp ? vxp[w * n * DIM + qd] : (qd == dir ? 1.0f : 0.0f);
+      }
+    };
     const float hval = p.t[w];
     const float bet = p.has_beta ? p.beta[w] : 0.f;
-    const float vh = (!MULTI && q.vh) ? q.vh[w] : 0.f;
+    const float vh = (!MULTI && !PROBE && q.vh) ? q.vh[w] : 0.f;
     // score_net.py:26-29 and their h-derivatives
     const float c_s = 1.0f / (1.0f + hval), c_in = 1.0f / sqrtf(1.0f + hval), sh = sqrtf(hval);
     const float c_out = sh * c_in, tfeat = 0.125f * logf(hval);
@@ -455,7 +471,7 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
     for (int qd = lane; qd < n * DIM; qd += 64) {
       const int i = qd / DIM, k = qd - i * DIM;
       const float xv = p.x[w * n * DIM + qd];
-      const float dx = vxp ? vxp[w * n * DIM + qd] : (qd == dir ? 1.0f : 0.0f);
+      const float dx = dx_at(qd, i, k);
       const float v = c_in * xv, dv = fmaf(c_in, dx, (vh * dc_in) * xv);
       pos[i * 4 + k] = v; pos0[i * 4 + k] = v;
       dpos[i * 4 + k] = dv; dpos0[i * 4 + k] = dv;
@@ -576,16 +592,19 @@ __global__ void __launch_bounds__(256) egnn_wide_jvp_kernel(WideJvpParams q) {
       const float F = (pos[i * 4 + k] - pos0[i * 4 + k]) - mean[k];
       const float dF = (dpos[i * 4 + k] - dpos0[i * 4 + k]) - dmean[k];
       const float xc = p.x[w * n * DIM + qd];
-      const float dx = vxp ? vxp[w * n * DIM + qd] : (qd == dir ? 1.0f : 0.0f);
+      const float dx = dx_at(qd, i, k);
       const float dD = fmaf(c_s, dx, fmaf(c_out, dF, vh * fmaf(dc_s, xc, dc_out * F)));
-      if (p.out && (!MULTI || dir == 0)) p.out[w * n * DIM + qd] = fmaf(c_s, xc, c_out * F);
-      if (!MULTI && q.dout) q.dout[w * n * DIM + qd] = dD;
-      dot = fmaf(xc, dD, dot);
+      if (p.out && (MULTI ? dir == 0 : PROBE ? probe == 0 : true)) p.out[w * n * DIM + qd] = fmaf(c_s, xc, c_out * F);
+      if (!MULTI && !PROBE && q.dout) q.dout[w * n * DIM + qd] = dD;
+      dot = fmaf(PROBE ? dx : xc, dD, dot);
       if (qd == dir) diag = dD;
     }
     if (MULTI) {
       const float s = wwave_sum(diag);
       if (lane == 0) q.diag_acc[(long long)dir * p.B + w] = s;
+    } else if (PROBE) {
+      const float s = wwave_sum(dot);
+      if (lane == 0) q.diag_acc[(long long)probe * p.B + w] = s;
     } else {
       if (q.dot_out) {
         const float s = wwave_sum(dot);
@@ -610,6 +629,34 @@ __global__ void __launch_bounds__(256) egnn_wide_trace_reduce_kernel(const float
   float s = 0.0f;
   for (int k = 0; k < ndir; ++k) s += diag[(long long)k * B + b];
   trace[b] = s;
+}
+
+// est[b] = (sum over the K probes, in probe order from +0, of qf[k * B + b]) / (float)K: the Hutchinson mean of the
+// quadratic forms the probe items left in the [K, B] scratch; per_probe (nullable [K, B]) takes a copy of them
+__global__ void __launch_bounds__(256) egnn_wide_probe_reduce_kernel(const float* __restrict__ qf, float* __restrict__ est,
+                                                                     float* __restrict__ per_probe, long long B, int K) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.0f;
+  for (int k = 0; k < K; ++k) {
+    const float v = qf[(long long)k * B + b];
+    if (per_probe) per_probe[(long long)k * B + b] = v;
+    s += v;
+  }
+  est[b] = s / (float)K;
+}
+
+// out[k, b, particle, :] = the Rademacher signs of probe k for walker walker_offset + b: the draw of the probe items above
+__global__ void __launch_bounds__(256) rademacher_probes_kernel(float* __restrict__ out, long long B, int n, int dim, int K,
+                                                                unsigned long long seed, unsigned long long walker_offset,
+                                                                long long step) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // (probe, walker, particle)
+  if (e >= (long long)K * B * n) return;
+  const int i = (int)(e % n);
+  const long long kb = e / n, b = kb % B;
+  const int k = (int)(kb / B);
+  const uint32_t word = philox_rademacher_word(seed, walker_offset + (unsigned long long)b, step, (uint32_t)k, (uint32_t)i);
+  for (int c = 0; c < dim; ++c) out[e * dim + c] = rademacher_sign(word, c);
 }
 
 }  // namespace
@@ -1092,7 +1139,7 @@ extern "C" int pita_egnn_wide_jvp(pita_egnn_wide_t* net, const float* h, const f
   // the vector-pipe kernel below computes exactly those
   if (wide_plan(net).jvp) {
     int rc = wide_jvp_marks(net, B, st);
-    if (rc == PITA_OK) rc = wide64_jvp(net, q, false, net->jbad.as<int>(), st);
+    if (rc == PITA_OK) rc = wide64_jvp(net, q, WIDE_JVP_ONE, net->jbad.as<int>(), st);
     if (rc != PITA_OK) return rc;
     q.only_bad = net->jbad.as<int>();
   }
@@ -1123,18 +1170,79 @@ extern "C" int pita_egnn_wide_jacobian_trace(pita_egnn_wide_t* net, const float*
   q.dir = -1; q.diag_acc = net->jdiag.as<float>();
   if (wide_plan(net).jvp) {
     int rc = wide_jvp_marks(net, items, st);
-    if (rc == PITA_OK) rc = wide64_jvp(net, q, true, net->jbad.as<int>(), st);
+    if (rc == PITA_OK) rc = wide64_jvp(net, q, WIDE_JVP_UNIT, net->jbad.as<int>(), st);
     if (rc != PITA_OK) return rc;
     q.only_bad = net->jbad.as<int>();
   }
   WideGrid g;
   int rc = wide_grid("pita_egnn_wide_jacobian_trace", net, wide_jvp_per_wave(p.n), kWideLdsOneBlock, 2, items, g);
   if (rc != PITA_OK) return rc;
-  rc = wide_launch("pita_egnn_wide_jacobian_trace", p.H <= 32 ? egnn_wide_jvp_kernel<32, true> : egnn_wide_jvp_kernel<64, true>,
+  rc = wide_launch("pita_egnn_wide_jacobian_trace", p.H <= 32 ? egnn_wide_jvp_kernel<32, WIDE_JVP_UNIT> : egnn_wide_jvp_kernel<64, WIDE_JVP_UNIT>,
                    g, q, st);
   if (rc != PITA_OK) return rc;
   hipLaunchKernelGGL(egnn_wide_trace_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, q.diag_acc, trace,
                      (long long)B, ndir);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// Hutchinson estimate of trace(J_x D) from n_probes probes in ONE call (the estimator beside compute_divergence_exact in the
+// reference's utils.py): one launch over (walker, probe) items -- same kernels, same arithmetic per item as
+// pita_egnn_wide_jvp(vx = v_k), same repair contract per item as pita_egnn_wide_jacobian_trace -- and a reduction that
+// adds the quadratic forms <v_k, dD> in probe order and divides by n_probes
+extern "C" int pita_egnn_wide_trace_probes(pita_egnn_wide_t* net, const float* h, const float* x, const float* beta,
+                                           int n_probes, const float* probes, uint64_t seed, uint64_t walker_offset,
+                                           int64_t step, float* estimate, float* per_probe, float* denoiser_out, int64_t B,
+                                           void* stream) {
+  PITA_REQUIRE(net && B >= 0, "pita_egnn_wide_trace_probes: bad argument");
+  PITA_REQUIRE(n_probes >= 1, "pita_egnn_wide_trace_probes: n_probes must be at least 1");
+  PITA_REQUIRE(probes || (n_probes <= kMaxDrawnProbes && net->cfg.n_particles <= kMaxProbeParticles),
+               "pita_egnn_wide_trace_probes: probes drawn in the kernel need n_probes <= %d and n_particles <= %d",
+               kMaxDrawnProbes, kMaxProbeParticles);
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(h && x && estimate, "pita_egnn_wide_trace_probes: null argument");
+  PITA_REQUIRE(beta || !net->cfg.condition_beta, "pita_egnn_wide_trace_probes: beta required (condition_beta)");
+  PitaDeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  WideJvpParams q{};
+  WideParams& p = q.base;
+  p = wide_params(net, B, 1);
+  p.x = x; p.t = h; p.beta = beta; p.out = denoiser_out;
+  const long long items = (long long)B * n_probes;
+  PITA_HIP_CHECK(net->jdiag.grow(sizeof(float) * (size_t)items, st));
+  q.dir = -1; q.diag_acc = net->jdiag.as<float>();
+  q.n_probes = n_probes; q.probes = probes; q.seed = seed; q.walker_offset = walker_offset; q.step = step;
+  if (wide_plan(net).jvp) {
+    int rc = wide_jvp_marks(net, items, st);
+    if (rc == PITA_OK) rc = wide64_jvp(net, q, WIDE_JVP_PROBE, net->jbad.as<int>(), st);
+    if (rc != PITA_OK) return rc;
+    q.only_bad = net->jbad.as<int>();
+  }
+  WideGrid g;
+  int rc = wide_grid("pita_egnn_wide_trace_probes", net, wide_jvp_per_wave(p.n), kWideLdsOneBlock, 2, items, g);
+  if (rc != PITA_OK) return rc;
+  rc = wide_launch("pita_egnn_wide_trace_probes",
+                   p.H <= 32 ? egnn_wide_jvp_kernel<32, WIDE_JVP_PROBE> : egnn_wide_jvp_kernel<64, WIDE_JVP_PROBE>, g, q, st);
+  if (rc != PITA_OK) return rc;
+  hipLaunchKernelGGL(egnn_wide_probe_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, q.diag_acc, estimate,
+                     per_probe, (long long)B, n_probes);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// The Rademacher probes pita_egnn_wide_trace_probes draws in its kernels for the same key, written out: [K, B, n*d]
+extern "C" int pita_rademacher_probes(float* out, int64_t B, int n_particles, int n_dim, int n_probes, uint64_t seed,
+                                      uint64_t walker_offset, int64_t step, void* stream) {
+  PITA_REQUIRE(B >= 0 && n_particles >= 1 && n_particles <= kMaxProbeParticles && n_dim >= 1 && n_dim <= 32 &&
+                   n_probes >= 1 && n_probes <= kMaxDrawnProbes,
+               "pita_rademacher_probes: needs 1 <= n_particles <= %d, 1 <= n_dim <= 32, 1 <= n_probes <= %d",
+               kMaxProbeParticles, kMaxDrawnProbes);
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(out, "pita_rademacher_probes: null argument");
+  const long long count = (long long)n_probes * B * n_particles;
+  hipLaunchKernelGGL(rademacher_probes_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out,
+                     (long long)B, n_particles, n_dim, n_probes, (unsigned long long)seed, (unsigned long long)walker_offset,
+                     (long long)step);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

@@ -75,6 +75,7 @@ struct Wide64Row {
   Wide64Kernel<P> k;
   Wide64Kernel<P> alt;        // forward: the small-batch mapping (fn null: none); forward mode: (walker, direction) items
   size_t (*ck_item_f)(int);   // reverse mode: floats of checkpoint scratch per resident item
+  Wide64Kernel<P> probes;     // forward mode: (walker, probe) items
 };
 template <class C>
 static size_t wide64_lds_of(int L) { return C::lds_bytes(L); }

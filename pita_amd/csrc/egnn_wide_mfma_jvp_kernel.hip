@@ -38,7 +38,13 @@ struct Wide64JvpParams {
   float* dot_out;    // nullable: dot_out[b * dot_stride + dot_off] = <x_b, dD_b>
   long long dot_stride, dot_off;
   float* diag_acc;   // nullable: diag_acc[b] += dD[b, dir]; MULTI: [N*DIM, B], diag_acc[dir * B + b] = dD[b, dir]
-  int* bad;          // [B] (MULTI: [B * N*DIM], one per item), zeroed by the launch wrapper: 1 = left to the vector-pipe kernel
+  int* bad;          // [B] (MULTI: [B * N*DIM], PROBE: [B * n_probes], one per item), zeroed by the launch wrapper: 1 = left
+                     // to the vector-pipe kernel
+  // PROBE items, as WideJvpParams
+  int n_probes;
+  const float* probes;
+  unsigned long long seed, walker_offset;
+  long long step;
 };
 
 template <int N, int DIM, int WAVES>
@@ -59,9 +65,16 @@ struct Wide64JvpCfg {
 // walker's inputs), each computed exactly as the single-direction launch with vx = vh = null computes it; the item's
 // diagonal entry dD[dir] goes to its own slot (plain store), the item of direction 0 writes the denoiser row; vx, vh, dir,
 // dout and dot_out are ignored.
-template <int N, int DIM, int WAVES, bool ATT, bool TANH, bool MULTI = false>
+// PROBE: the work items are (walker, probe) pairs, item = walker * n_probes + probe, each computed exactly as the
+// single-direction launch with vx = v_probe, vh = null computes it -- v_probe row [probe, walker] of `probes`, or, without
+// it, Rademacher signs drawn here (common.h: philox_rademacher_word; bit k of the column's word is coordinate k) --; the
+// item's quadratic form <v_probe, dD>, summed on the path of dot_out's <x, dD> (within a column over the coordinates,
+// then over columns 0 .. N-1), goes to its own slot diag_acc[probe * B + walker] (plain store), the item of probe 0 writes
+// the denoiser row; vx, vh, dir, dout and dot_out are ignored.
+template <int N, int DIM, int WAVES, bool ATT, bool TANH, int KIND = WIDE_JVP_ONE>
 __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64JvpParams p) {
   using C = Wide64JvpCfg<N, DIM, WAVES>;
+  constexpr bool MULTI = KIND == WIDE_JVP_UNIT, PROBE = KIND == WIDE_JVP_PROBE;
   static_assert(C::NT * C::IPB == WAVES && C::NT <= 2, "NT waves per item, one per column tile");
   constexpr int NT = C::NT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -88,7 +101,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
   const int live = valid ? 1 : 0;
 
   constexpr int NDIR = N * DIM;
-  const long long items = MULTI ? p.B * NDIR : p.B;
+  const long long items = MULTI ? p.B * NDIR : PROBE ? p.B * p.n_probes : p.B;
   // block-uniform trip count (the NT == 2 body holds block barriers): a slot past the last item computes that item again
   // in its own tables and writes nothing (at most one wasted item per block and launch, in the block's last trip); with
   // one wave per item such a wave has no barrier to keep and leaves
@@ -96,12 +109,16 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
     const bool active = base + slot < items;
     if (NT == 1 && !active) break;
     const long long item = active ? base + slot : items - 1;
-    const long long w = MULTI ? item / NDIR : item;
-    const int dir = MULTI ? (int)(item - w * NDIR) : p.dir;
-    const float* const vxp = MULTI ? nullptr : p.vx;
+    const long long w = MULTI ? item / NDIR : PROBE ? item / p.n_probes : item;
+    const int dir = MULTI ? (int)(item - w * NDIR) : PROBE ? -1 : p.dir;
+    const int probe = PROBE ? (int)(item - w * p.n_probes) : 0;
+    const float* const vxp = MULTI ? nullptr : PROBE ? (p.probes ? p.probes + (long long)probe * p.B * NDIR : nullptr) : p.vx;
     const float hv = p.h[w];
     const float bet = p.has_beta ? p.beta[w] : 0.f;
-    const float vh = (!MULTI && p.vh) ? p.vh[w] : 0.f;
+    const float vh = (!MULTI && !PROBE && p.vh) ? p.vh[w] : 0.f;
+    uint32_t signs = 0;
+    if constexpr (PROBE)
+      if (!vxp) signs = philox_rademacher_word(p.seed, p.walker_offset + (unsigned long long)w, p.step, (uint32_t)probe, (uint32_t)nodei);
     // score_net.py:26-29 and their h-derivatives
     const float c_s = 1.0f / (1.0f + hv), c_in = 1.0f / sqrtf(1.0f + hv), sh = sqrtf(hv);
     const float c_out = sh * c_in, tfeat = 0.125f * logf(hv);
@@ -112,7 +129,8 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
     for (int k = 0; k < DIM; ++k) {
       const long long e = (w * N + col) * DIM + k;
       xin[k] = valid ? p.x[e] : 0.f;
-      dxin[k] = valid ? (vxp ? vxp[e] : ((col * DIM + k) == dir ? 1.0f : 0.0f)) : 0.f;
+      if constexpr (PROBE) dxin[k] = valid ? (vxp ? vxp[e] : rademacher_sign(signs, k)) : 0.f;
+      else dxin[k] = valid ? (vxp ? vxp[e] : ((col * DIM + k) == dir ? 1.0f : 0.0f)) : 0.f;
       const float ps = c_in * xin[k], dps = fmaf(c_in, dxin[k], (vh * dc_in) * xin[k]);
       if (hh == 0) {
         pos0[col * DIM + k] = ps; posbuf0[col * DIM + k] = ps;
@@ -301,11 +319,11 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
       dF[k] -= ds / (float)N;
       Dv[k] = fmaf(c_s, xin[k], c_out * F[k]);
       dD[k] = fmaf(c_s, dxin[k], fmaf(c_out, dF[k], vh * fmaf(dc_s, xin[k], dc_out * F[k])));
-      part = fmaf(xin[k], dD[k], part);
+      part = fmaf(PROBE ? dxin[k] : xin[k], dD[k], part);
       ok = ok && __builtin_isfinite(Dv[k]) && __builtin_isfinite(dD[k]);
     }
     item_fence<NT>();
-    float* red = scr;       // [NCOLP][2]: <x, dD> of the column, its non-finite flag
+    float* red = scr;       // [NCOLP][2]: <x, dD> (PROBE: <v, dD>) of the column, its non-finite flag
     if (hh == 0) { red[col * 2] = valid ? part : 0.f; red[col * 2 + 1] = (valid && !ok) ? 1.0f : 0.0f; }
     item_fence<NT>();
     float dot = 0.f, nbad = 0.f;
@@ -320,13 +338,16 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_wide64_jvp_kernel(Wide64Jv
         if (MULTI) {
           if (p.out && dir == 0) p.out[e] = Dv[k];
           if ((col * DIM + k) == dir) p.diag_acc[(long long)dir * p.B + w] = dD[k];
+        } else if (PROBE) {
+          if (p.out && probe == 0) p.out[e] = Dv[k];
         } else {
           if (p.out) p.out[e] = Dv[k];
           if (p.dout) p.dout[e] = dD[k];
           if (p.diag_acc && !p.vx && (col * DIM + k) == p.dir) p.diag_acc[w] += dD[k];
         }
       }
-      if (!MULTI && p.dot_out && col == 0) p.dot_out[w * p.dot_stride + p.dot_off] = dot;
+      if (PROBE && col == 0) p.diag_acc[(long long)probe * p.B + w] = dot;
+      if (!MULTI && !PROBE && p.dot_out && col == 0) p.dot_out[w * p.dot_stride + p.dot_off] = dot;
     }
     item_fence<NT>();
   }
@@ -338,24 +359,30 @@ template <int N, int DIM, int WAVES>
 static Wide64Row<Wide64JvpParams> wide64_jvp_row_of() {
   using C = Wide64JvpCfg<N, DIM, WAVES>;
 #define PITA_K(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T>
-#define PITA_KM(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T, true>
+#define PITA_KM(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T, WIDE_JVP_UNIT>
+#define PITA_KP(A, T) egnn_wide64_jvp_kernel<N, DIM, WAVES, A, T, WIDE_JVP_PROBE>
   return {N, DIM, {PITA_WIDE64_FNS(PITA_K), wide64_lds_of<C>, 1, WAVES, C::NT},
-          {PITA_WIDE64_FNS(PITA_KM), wide64_lds_of<C>, 1, WAVES, C::NT}};
+          {PITA_WIDE64_FNS(PITA_KM), wide64_lds_of<C>, 1, WAVES, C::NT}, nullptr,
+          {PITA_WIDE64_FNS(PITA_KP), wide64_lds_of<C>, 1, WAVES, C::NT}};
 #undef PITA_K
 #undef PITA_KM
+#undef PITA_KP
 }
 static const Wide64Row<Wide64JvpParams> kWide64JvpRows[] = {wide64_jvp_row_of<22, 3, 4>(), wide64_jvp_row_of<33, 3, 4>(),
                                                             wide64_jvp_row_of<42, 3, 4>()};
 
 const Wide64Row<Wide64JvpParams>* wide64_jvp_row(const pita_egnn_wide_config& cfg) { return wide64_find(kWide64JvpRows, cfg); }
 
-int wide64_jvp(pita_egnn_wide* net, const WideJvpParams& v, bool multi, int* bad, hipStream_t stream) {
+int wide64_jvp(pita_egnn_wide* net, const WideJvpParams& v, int kind, int* bad, hipStream_t stream) {
   Wide64JvpParams p = wide64_params<Wide64JvpParams>(net, v.base.B);
   p.x = v.base.x; p.h = v.base.t; p.beta = v.base.beta; p.out = v.base.out;
   p.vx = v.vx; p.vh = v.vh; p.dir = v.dir; p.dout = v.dout; p.dot_out = v.dot_out; p.dot_stride = v.dot_stride;
   p.dot_off = v.dot_off; p.diag_acc = v.diag_acc; p.bad = bad;
-  const Wide64Kernel<Wide64JvpParams>& k = multi ? net->jvp64->alt : net->jvp64->k;
-  const long long items = multi ? p.B * net->cfg.n_particles * net->cfg.n_dim : p.B;
+  p.n_probes = v.n_probes; p.probes = v.probes; p.seed = v.seed; p.walker_offset = v.walker_offset; p.step = v.step;
+  const Wide64Kernel<Wide64JvpParams>& k =
+      kind == WIDE_JVP_UNIT ? net->jvp64->alt : kind == WIDE_JVP_PROBE ? net->jvp64->probes : net->jvp64->k;
+  const long long items =
+      kind == WIDE_JVP_UNIT ? p.B * net->cfg.n_particles * net->cfg.n_dim : kind == WIDE_JVP_PROBE ? p.B * v.n_probes : p.B;
   return wide64_launch(net, k, wide64_grid(net, k, items), p, stream);
 }
 

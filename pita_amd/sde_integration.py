@@ -44,6 +44,7 @@ def _quantile_clamp(a, q):
     return a
 
 
+PROBE_STREAM_ID = 3  # WeightedSDEIntegrator._key: the Hutchinson probes' stream (0: noise, 1 and 2: the MALA chains)
 _STEP_TABLES = {}  # key -> table; the last few (schedule, grid) combinations of this process
 
 
@@ -289,6 +290,8 @@ class WeightedSDEIntegrator:
         return model if fused else None
 
     def _key(self, stream_id):
+        """Philox seed of one of a run's independent streams: 0 the Euler-Maruyama noise, 1 and 2 the MALA chains,
+        PROBE_STREAM_ID the Hutchinson probes of ``VEReverseSDE(divergence="hutchinson")``."""
         return (int(self.seed) * 0x9E3779B97F4A7C15 + (self._runs << 8) + stream_id) & 0xFFFFFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ A1 integrate_sde
@@ -407,6 +410,8 @@ class WeightedSDEIntegrator:
             st4 = torch.zeros(N, 4, dtype=torch.float64, device=dev)
             st8 = torch.zeros(N, 8, dtype=torch.float64, device=dev)
         st = _lib.stream_ptr(dev)
+        # this run's _key(PROBE_STREAM_ID): `key` is its _key(0)
+        probe_seed = (key + PROBE_STREAM_ID) & 0xFFFFFFFFFFFFFFFF
         for step in range(N):
             t = times[step]  # host scalar: the schedules' scalars (gamma, dgamma/dt) are then read without a device sync
             row = tab_h[step]
@@ -416,7 +421,12 @@ class WeightedSDEIntegrator:
                 num_unique_idxs.append(Bg)
                 continue
             # one set of launches for the rank's whole shard; the quantile clamp keeps its per-chunk meaning
-            terms = self.sde.f(t, x, beta, gamma_schedule, None, energy_function, resampling_interval, clamp_chunk=bs)
+            kw = {}
+            if getattr(self.sde, "divergence", "exact") == "hutchinson":
+                # keyed like the noise -- by run, GLOBAL walker index and step --: bitwise repeatable, independent of the
+                # number of ranks, and the two copies of a resampled parent draw different probes
+                kw["probe_key"] = (probe_seed, off, step)
+            terms = self.sde.f(t, x, beta, gamma_schedule, None, energy_function, resampling_interval, clamp_chunk=bs, **kw)
             drift = terms.drift_X.contiguous()
             nz = noise[step].contiguous() if noise is not None else None
             _lib.check(L.pita_em_step(x.data_ptr(), drift.data_ptr(), _lib.ptr(nz), Bl, n, d, float(row[_lib.ST_DT]),

@@ -16,6 +16,10 @@
   (pita_mlp_jacobian, csrc/mlp_jac_kernel.hip) whose D unit tangents and h tangent share the primal's weight stream
   and give J_x D^T x, <x, dD/dh> and the trace in-kernel.  Per step; the clamp is pita_quantile_clamp per inference
   chunk.  Any backbone with ``jvp`` (and optionally ``vjp`` / ``jacobian_trace``) runs this regime.
+  ``VEReverseSDE(divergence="hutchinson", n_probes=K)`` replaces the exact trace by the Hutchinson estimate the
+  reference's utils.py ships beside ``compute_divergence_exact``: mean over K Rademacher probes of <v, J_x D v>
+  (``jacobian_trace_estimate`` on the wide EGNN: pita_egnn_wide_trace_probes, one call; K ``jvp`` launches elsewhere).
+  The log-weight drift then carries zero-mean estimator noise; the default stays exact.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -104,13 +108,24 @@ def _per_walker(t, x):
 
 class VEReverseSDE:
     def __init__(self, noise_schedule, energy_net=None, score_net=None, cdf=None, pin_energy=False,
-                 debias_inference=True):
+                 debias_inference=True, divergence="exact", n_probes=None):
+        """``divergence`` (extension): "exact" -- trace(J_x D) over all n*d unit directions, the default -- or
+        "hutchinson" -- its unbiased estimate from ``n_probes`` >= 1 Rademacher probes (utils.py's estimator), drawn
+        per (probe_key of ``f``, global walker index): n_probes / (n*d) of the exact trace's work."""
+        if divergence not in ("exact", "hutchinson"):
+            raise ValueError(f"divergence must be 'exact' or 'hutchinson', got {divergence!r}")
+        if divergence == "hutchinson":
+            if n_probes is None or isinstance(n_probes, bool) or int(n_probes) != n_probes or int(n_probes) < 1:
+                raise ValueError(f"divergence='hutchinson' needs an integer n_probes >= 1, got {n_probes!r}")
+            n_probes = int(n_probes)
+        self.divergence, self.n_probes = divergence, n_probes
         self.noise_schedule = noise_schedule
         self.energy_net, self.score_net = energy_net, score_net
         self.pin_energy = pin_energy
         self.debias_inference = debias_inference
-        # accepted for interface compatibility and ignored: the exact divergence comes from the backbone's own
-        # multi-direction kernel (EGNN_dynamics.jacobian_trace), not from a torch.compile'd vmap(jacrev) closure
+        # accepted for interface compatibility and ignored: `divergence` selects between the exact trace of the backbone's
+        # own multi-direction kernel (jacobian_trace) and its Hutchinson estimate (jacobian_trace_estimate), not a
+        # torch.compile'd closure
         self.compiled_divergence_fn = cdf
         self.trainer = None  # set from outside by the reference (energytemp_module.py:1295)
 
@@ -125,10 +140,12 @@ class VEReverseSDE:
         return SDETerms(drift_X=drift_X.detach(), drift_A=torch.zeros(x.shape[0], device=x.device))
 
     def f(self, t, x, beta, gamma_energy_schedule, gamma_score, energy_function, resampling_interval=-1,
-          clamp_chunk=None):
+          clamp_chunk=None, probe_key=(0, 0, 0)):
         """``clamp_chunk`` (extension): evaluate the whole batch in one set of launches but apply the 0.9-quantile
         clamp of the weight drift per chunk of that many walkers -- what the reference gets by calling ``f`` once per
-        inference chunk (sde_integration.py:312-343, sdes.py:230), without its per-chunk launch overhead."""
+        inference chunk (sde_integration.py:312-343, sdes.py:230), without its per-chunk launch overhead.
+        ``probe_key`` (extension) = (seed, walker_offset, step): the Philox key of the Rademacher probes under
+        ``divergence="hutchinson"`` (row b draws for walker walker_offset + b); ignored by the exact divergence."""
         if self.debias_inference and isinstance(t, torch.Tensor) and t.dim() == 0 and t.device.type != "cpu":
             # a 0-dim DEVICE step time is the same thing as the integrator's host scalar: one read up front, then the
             # scalar path -- the schedule is evaluated by the same (host) code either way, so both give the same bits
@@ -148,7 +165,7 @@ class VEReverseSDE:
             sched_scalars = (float(self.noise_schedule.h(t1)[0]), float(self.g(t1).pow(2)[0]), float(self._dh_dt(t1)[0]))
         t = _per_walker(t, x)
         return self.f_debiased(t, x, beta, gamma_energy, gamma_energy_schedule, clamp_chunk, energy_function, dgamma,
-                               sched_scalars)
+                               sched_scalars, probe_key)
 
     # ------------------------------------------------------------------ debiased regime (sdes.py:151-239)
     def _denoiser_jacobian_terms(self, model, ht, x, beta, want_h_direction):
@@ -183,9 +200,38 @@ class VEReverseSDE:
         D_E, jtx, dot_h = model.vjp(ht, x, beta, want_dot_h=True)  # <x, dD/dh> rides on the reverse sweep
         return D_E, jtx, dot_h, None
 
-    def _score_divergence_terms(self, model, ht, x, beta):
+    def _score_divergence_terms(self, model, ht, x, beta, probe_key=(0, 0, 0)):
         """D and trace(J_x D) of the score net's denoiser from the multi-direction divergence kernel (dim / K launches;
-        D is a by-product of the first one); backbones without it use dim single-direction JVP launches."""
+        D is a by-product of the first one); backbones without it use dim single-direction JVP launches.
+        ``divergence="hutchinson"``: the Hutchinson estimate in the trace's place -- the backbone's one-call
+        ``jacobian_trace_estimate`` where it has one, else n_probes ``jvp(vx=v_k)`` launches on probes drawn by
+        ``rademacher_probes`` and the mean of the <v_k, dD_k>, formed on the device in probe order."""
+        if self.divergence == "hutchinson":
+            seed, off, step = probe_key
+            K = self.n_probes
+            if hasattr(model, "jacobian_trace_estimate"):
+                est, D_S, _ = model.jacobian_trace_estimate(ht, x, beta, K, seed=seed, walker_offset=off, step=step,
+                                                            want_denoiser=True)
+                return D_S, est
+            if not hasattr(model, "jvp"):
+                raise NotImplementedError(
+                    "debias_inference=True needs a backbone with a forward-mode derivative (jvp: the HIP EGNN and MLP backbones)")
+            from .utils import rademacher_probes
+
+            B, D = x.shape
+            n = int(getattr(model, "_n_particles", None) or 1)
+            if D % n:
+                n = 1
+            if n > 1023 or D // n > 32:  # what one Philox word per particle serves: one "particle" per coordinate
+                n = D
+            probes = rademacher_probes(B, n, D // n, K, seed=seed, walker_offset=off, step=step, device=x.device)
+            acc = torch.zeros(B, device=x.device)
+            D_S = None
+            for k in range(K):
+                out, dout = model.jvp(ht, x, beta, vx=probes[k], want_primal=(k == 0), want_tangent=True)
+                D_S = out if k == 0 else D_S
+                acc = acc + (probes[k] * dout).sum(-1)
+            return D_S, acc / float(K)
         if not hasattr(model, "jacobian_trace"):
             D_S, trace, _, _ = self._denoiser_jacobian_terms(model, ht, x, beta, False)
             return D_S, trace
@@ -203,7 +249,7 @@ class VEReverseSDE:
             return torch.autograd.grad(sched.h(tt).sum(), tt)[0]
 
     def f_debiased(self, t, x, beta, gamma_energy, gamma_energy_schedule, clamp_chunk=None, energy_function=None,
-                   dgamma_dt=None, sched_scalars=None):
+                   dgamma_dt=None, sched_scalars=None, probe_key=(0, 0, 0)):
         assert self.energy_net is not None
         if self.score_net is None:
             # sdes.py:204-216 (Laplacian of E_theta by vmap(hessian)).  Unreachable in the reference as shipped: its
@@ -242,7 +288,7 @@ class VEReverseSDE:
         dg = gamma_energy_schedule.dgamma_dt(t) if dgamma_dt is None else dgamma_dt
         dgamma = float(dg.reshape(-1)[0]) if isinstance(dg, torch.Tensor) else float(dg)
         D_E, jtx_E, dot_h, h_parts = self._energy_gradient_terms(self.energy_net.net, ht, x, beta)
-        D_S, trace_S = self._score_divergence_terms(self.score_net.model, ht, x, beta)
+        D_S, trace_S = self._score_divergence_terms(self.score_net.model, ht, x, beta, probe_key)
         drift_X = torch.empty_like(x)
         drift_A, div_bt, cross, dUdt, Ut = (torch.empty(B, device=x.device) for _ in range(5))
         _lib.check(_lib.lib().pita_fk_assemble(

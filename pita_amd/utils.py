@@ -22,6 +22,20 @@ def sample_cat_sys(bs, logits, u=None):
     return ids, None
 
 
+def rademacher_probes(B, n_particles, n_dim, n_probes, seed=0, walker_offset=0, step=0, device="cuda"):
+    """[n_probes, B, n_particles * n_dim] Rademacher probes (+1 / -1) of the Hutchinson divergence estimator (the one
+    the reference's utils.py ships beside ``compute_divergence_exact``) from the library's Philox stream
+    (pita_rademacher_probes): row [k, b] is what the probe kernels of ``jacobian_trace_estimate(probes=None)`` draw for
+    probe k of walker ``walker_offset + b`` under the same (seed, step).  1 <= n_probes <= 256."""
+    device = torch.device(device)
+    out = torch.empty(int(n_probes), int(B), int(n_particles) * int(n_dim), device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().pita_rademacher_probes(out.data_ptr(), int(B), int(n_particles), int(n_dim), int(n_probes),
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step),
+                                                     _lib.stream_ptr(device)), "pita_rademacher_probes")
+    return out
+
+
 def gather_rows(x, ids):
     """x[ids] through the HIP row-gather kernel."""
     x = _lib.dev_tensor(x, "x")

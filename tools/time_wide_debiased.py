@@ -1,6 +1,8 @@
 """Debiased (Feynman-Kac) step with the alanine-dipeptide backbone EGNN_dynamics_AD2_cat (hidden 64 x 5) for score and
 energy net: forward-mode launches (pita_egnn_wide_jvp) for the trace, one reverse-mode launch (pita_egnn_wide_vjp), config C4's per-GPU shard by default.
-python tools/time_wide_debiased.py [walkers]"""
+python tools/time_wide_debiased.py [walkers] [K,K...]
+K,K...: also the step with VEReverseSDE(divergence="hutchinson", n_probes=K) for each K, interleaved with the exact step
+(median of 5 alternating repetitions each)."""
 import copy, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,3 +36,26 @@ step = ev(lambda: sde.f(t, x, 1.0, gam, None, None, resampling_interval=1))
 print(f"B={B}: denoiser forward {fwd*1e3:.2f} ms (matrix pipe), {fwd_v*1e3:.2f} ms (vector pipe); one forward-mode launch "
       f"{one*1e3:.2f} ms; one reverse-mode launch {rev*1e3:.2f} ms; debiased step (67 forward-mode launches + 1 "
       f"reverse-mode launch) {step*1e3:.1f} ms = {B/step:.3e} walker-steps/s")
+if len(sys.argv) > 2:
+    import statistics
+    Ks = [int(k) for k in sys.argv[2].split(",")]
+    sdes = {0: sde}
+    for K in Ks:
+        sdes[K] = pa.VEReverseSDE(noise_schedule=sched, score_net=pa.ScoreNet(net), energy_net=sde.energy_net,
+                                  debias_inference=True, divergence="hutchinson", n_probes=K)
+    run = lambda K: sdes[K].f(t, x, 1.0, gam, None, None, resampling_interval=1, probe_key=(7, 0, 3))
+    for K in sdes:
+        run(K)
+    torch.cuda.synchronize()
+    ts = {K: [] for K in sdes}
+    for _ in range(5):
+        for K in sdes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); run(K); e1.record(); e1.synchronize()
+            ts[K].append(e0.elapsed_time(e1))
+    m0 = statistics.median(ts[0])
+    for K in sdes:
+        m = statistics.median(ts[K])
+        name = "exact divergence" if K == 0 else f"Hutchinson K={K}"
+        print(f"B={B}: debiased step, {name}: median {m:.2f} ms (min {min(ts[K]):.2f}, max {max(ts[K]):.2f}) = "
+              f"{m / m0:.3f} of exact, {B / (m * 1e-3):.3e} walker-steps/s")
