@@ -415,6 +415,31 @@ int pita_egnn_div_accumulate(pita_egnn_t* net, const float* h, const float* x, c
 int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const float* x, const float* beta, float* trace,
                              float* denoiser_out /*nullable*/, int64_t B, void* stream);
 
+/* Hutchinson estimate of trace(J_x D)(h, x) from n_probes = K probes and, optionally, D itself, on the hidden-32 EGNN:
+ * ONE call (arguments and contract of pita_egnn_wide_trace_probes).  estimate[b] = (sum_k q[k, b], added in probe order
+ * from +0) / (float)K with q[k, b] = <v_k, J_x D v_k>; per_probe (nullable) receives q.  The probes go through the
+ * multi-direction kernels of pita_egnn_div_accumulate with probes in the place of unit vectors, K_launch =
+ * pita_egnn_div_directions(net) of them per launch sharing ONE primal evaluation: ceil(K / K_launch) launches (the last
+ * one may be short) and one small reduction, against K pita_egnn_jvp launches that each recompute the primal.
+ * Precision-2 handles run the f16 kernel, which leaves the probes of a walker with a non-finite term unwritten and marks
+ * it, then the bf16x3 kernel on exactly the marked walkers; other precisions run the bf16x3 kernel.  Per (walker, probe)
+ * q = sum_{i,c} v_ic [c_s v_ic + c_out (dF_ic - (1/N) sum_j dF_jc)] is summed by one lane in (particle, coordinate) order
+ * and stored once: no atomics, so a walker's q, estimate and D bits depend on neither B, its row, walker_offset beyond
+ * its own global index, the number of probes in the call nor the launch slot a probe lands in.  denoiser_out comes from
+ * the first launch and has the bits of pita_egnn_jacobian_trace's on the same handle.  q lives in per_probe when given,
+ * else in a handle-owned [K, B] buffer.
+ * probes != NULL: v_k = probes[k, b, :], arbitrary floats (parity hook).  probes == NULL: Rademacher signs drawn in the
+ * kernels with the key, tag and bit convention of pita_egnn_wide_trace_probes -- what pita_rademacher_probes writes out
+ * for the same (seed, walker_offset, step); needs K <= 256.
+ * B = 0 is PITA_OK and touches nothing; a null net / h / x / estimate, n_probes < 1, K > 256 on the drawn path or a
+ * missing beta with in_node_nf == 2 is PITA_EINVAL before any device call; a particle system without a multi-direction
+ * kernel (pita_egnn_div_directions < 0) is PITA_EUNSUPPORTED. */
+int pita_egnn_trace_probes(pita_egnn_t* net, const float* h, const float* x, const float* beta /*nullable*/,
+                           int n_probes, const float* probes /*nullable [K,B,n*d]*/, uint64_t seed,
+                           uint64_t walker_offset, int64_t step, float* estimate /*[B]*/,
+                           float* per_probe /*nullable [K,B]*/, float* denoiser_out /*nullable [B,n*d]*/, int64_t B,
+                           void* stream);
+
 /* Work accounting for the roofline of the debiased leg (bench.py): matrix-core wave-instructions per walker for one full
  * trace (all n_particles * n_dim directions) on the path this handle takes; units as pita_egnn_sampler_work. */
 int pita_egnn_div_work(const pita_egnn_t* net, double* mfma16_per_walker, double* mfma32_per_walker);

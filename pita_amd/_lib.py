@@ -112,6 +112,8 @@ _PROTOS = {
     "pita_egnn_div_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                          c_int64, c_void_p]),
     "pita_egnn_jacobian_trace": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pita_egnn_trace_probes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_uint64,
+                                       c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pita_egnn_div_work": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "pita_fk_assemble": (c_int, [c_void_p] * 10 + [c_float, c_float, c_void_p, c_void_p, c_float, c_float, c_void_p] +
                          [c_void_p] * 6 + [c_int64, c_int, c_void_p]),
@@ -183,7 +185,9 @@ def last_error() -> str:
 
 def check(rc: int, what: str = ""):
     if rc != 0:
-        raise PitaHipError(f"{what or 'libpita_hip'} failed (code {rc}): {last_error()}")
+        err = PitaHipError(f"{what or 'libpita_hip'} failed (code {rc}): {last_error()}")
+        err.code = rc
+        raise err
 
 
 def stream_ptr(device=None) -> int:

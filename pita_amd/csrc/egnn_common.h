@@ -379,6 +379,8 @@ struct pita_egnn {
   int* d_mark = nullptr;         // precision 2 divergence kernel: walkers left to the bf16x3 kernel (egnn_div_kernel.hip)
   size_t mark_bytes = 0;         // capacity of the marks; one flag word sits behind them (egnn_div_kernel.hip: bad_flag)
   int div_seq = 0;               // sequence number of the last launch that could mark walkers
+  float* d_probe_q = nullptr;    // [n_probes, B] quadratic forms of pita_egnn_trace_probes when the caller takes only the mean
+  size_t probe_q_bytes = 0;
   void* d_bk = nullptr;          // precision 2 sampler: walker backup + owed-moments markers for the repair launch
   size_t bk_bytes = 0;
 };

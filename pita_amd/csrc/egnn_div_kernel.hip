@@ -10,7 +10,8 @@
 // per SIMD the instruction-level parallelism it lacks in the one-direction kernel -- reuse it.  (Only 256 of the
 // wave's 512 registers are visible to VALU instructions, so per-node tangent state that the edge loop merely reads --
 // Wa dh_i -- is parked in LDS next to the partner tables.)  Output:
-// diag_acc[b] += sum_k (J_x D e_{dir0+k})_{dir0+k}.
+// diag_acc[b] += sum_k (J_x D e_{dir0+k})_{dir0+k}.  The same two kernels in probe mode (DivProbes) take K Hutchinson probes
+// v_k in the place of the unit vectors and store <v_k, J_x D v_k> per (walker, probe): pita_egnn_trace_probes.
 //
 // Mapping: as egnn_jvp_kernel.hip (wave = G walkers = dense 32-column tiles, lane = column x 16 features, exact 3-way
 // bf16 split on the matrix pipe, tangents in the lane/register position of their primals); one wave per SIMD.
@@ -50,7 +51,54 @@ struct DivParams {
                       // only, so moving every particle along k moves every pos^L_{i,k} by the same amount,
                       // sum_{i0} d pos^L_{i,k} / d x_{i0,k} = 1, and sum_d (sum_i d pos^L_{i,k_d} - 1) = dim N - N dim = 0.
                       // What is left of a direction's term needs the tangent of ONE output coordinate only.
+  // PROBE instantiations (pita_egnn_trace_probes): the K tangent inputs are the probes dir0 .. dir0 + ndir - 1 of each
+  // walker instead of unit vectors, and the launch writes their quadratic forms <v, J_x D v> instead of diagonal entries
+  const float* probes;      // nullable [n_probes, B, N*DIM]; null: Rademacher signs drawn in the kernel (common.h:
+                            // philox_rademacher_word keyed seed, walker_offset + walker, step, probe, particle)
+  unsigned long long seed, walker_offset;
+  long long step;
+  float* q_out;             // [n_probes, B]: q_out[probe * B + walker], plain stores (no_mean is not consulted: the
+                            // mean-free projection's share does not cancel for a probe)
 };
+
+// Row [probe, walker, node, :] of the probes: the injected floats, or the signs of the node's Philox word
+template <int N, int DIM>
+__device__ __forceinline__ void probe_values(const DivParams& p, int probe, long long wid, int node, float (&v)[DIM]) {
+  if (p.probes) {
+    const float* src = p.probes + (((long long)probe * p.B + wid) * N + node) * DIM;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) v[k] = src[k];
+  } else {
+    const uint32_t word = philox_rademacher_word(p.seed, p.walker_offset + (unsigned long long)wid, p.step, (uint32_t)probe,
+                                                 (uint32_t)node);
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) v[k] = rademacher_sign(word, k);
+  }
+}
+
+// Read-out of a PROBE launch, one lane per (walker w of the group, probe slot d): q = sum_{i,c} v_ic [c_s v_ic +
+// cf (dF_ic - (1/N) sum_j dF_jc)] in (node, coordinate) order, from the wave's LDS tables dscr (dF) and vtab (v), both
+// [K][POS_F]; cf = c_out where dF is the tangent of the scaled input's image, c_out c_in where it kept its true scale
+template <int N, int DIM, int POS_F>
+__device__ __forceinline__ float probe_quadratic_form(const float* dscr, const float* vtab, int w, int d, float c_s, float cf) {
+  const float* dF = dscr + d * POS_F + w * N * DIM;
+  const float* vv = vtab + d * POS_F + w * N * DIM;
+  float mean[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    float s = 0.f;
+    for (int j = 0; j < N; ++j) s += dF[j * DIM + c];
+    mean[c] = s / (float)N;
+  }
+  float q = 0.f;
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+      const float v = vv[i * DIM + c];
+      q = fmaf(v, fmaf(cf, dF[i * DIM + c] - mean[c], c_s * v), q);
+    }
+  return q;
+}
 
 template <int N, int DIM, int G, int WAVES, int K, int DAL = 1>  // DAL: Wa dh_i tables in LDS (1) or in registers (0)
 struct DivCfg {
@@ -73,9 +121,14 @@ __device__ __forceinline__ void silu_dsilu2(float v, float& y, float& g) {
   g = s * fmaf(v * (1.0f / SILU_PRESCALE), 1.0f - s, 1.0f);
 }
 
-template <int N, int DIM, int G, int WAVES, int K>
+// MODE: empty for the unit-direction kernel -- a pack, so that its symbol (which profiles and tests name) and its code
+// stay what they were before the probes --, DivProbes for the probe kernel
+struct DivProbes {};
+template <int N, int DIM, int G, int WAVES, int K, typename... MODE>
 __global__ void __launch_bounds__(WAVES * 64, 1) egnn_div_kernel(DivParams p) {
+  constexpr bool PROBE = sizeof...(MODE) > 0;
   using C = DivCfg<N, DIM, G, WAVES, K>;
+  static_assert(!PROBE || G * K <= 64, "probe read-out: one lane per (walker, probe slot)");
   constexpr int NT = C::NT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (p.repair && p.bad_flag && *p.bad_flag != p.bad_seq) return;  // the fast launch marked nobody
@@ -134,6 +187,11 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_div_kernel(DivParams p) {
       c_in[T] = rs;
       c_out[T] = sqrtf(hv) * rs;
       const float tfeat = 0.125f * logf(hv);
+      [[maybe_unused]] float pv[PROBE ? K : 1][DIM];
+      if constexpr (PROBE) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) probe_values<N, DIM>(p, dir0 + (q < ndir ? q : 0), wid, nodei[T], pv[q]);
+      }
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
         const long long gi = (walker0 * N + col[T]) * DIM + k;
@@ -146,7 +204,9 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_div_kernel(DivParams p) {
         }
 #pragma unroll
         for (int q = 0; q < K; ++q) {
-          const float v = (valid[T] && q < ndir && nodei[T] * DIM + k == dir0 + q) ? c_in[T] : 0.f;  // d(c_in x)
+          float v;  // d(c_in x)
+          if constexpr (PROBE) v = (valid[T] && q < ndir) ? c_in[T] * pv[q][k] : 0.f;
+          else v = (valid[T] && q < ndir && nodei[T] * DIM + k == dir0 + q) ? c_in[T] : 0.f;
           dposi[T][q][k] = v;
           dp0i[T][q][k] = v;
           if (hh == 0) {
@@ -364,6 +424,35 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_div_kernel(DivParams p) {
           dposi[T][d][k] -= dp0i[T][d][k];  // dF
           if (hh == 0) dscr[d * C::POS_F + col[T] * DIM + k] = dposi[T][d][k];
         }
+    if constexpr (PROBE) {
+      // q = <v, dD>, dD = c_s v + c_out (dF - mean dF): the probes again (Wa dh_i's table is free now), then one lane per
+      // (walker, probe slot) sums in a fixed order and stores once
+      float* vtab = dA;  // [K][NCOLP*DIM]
+#pragma unroll
+      for (int T = 0; T < NT; ++T) {
+        const long long wid = valid[T] ? walker0 + col[T] / N : p.B - 1;
+#pragma unroll
+        for (int d = 0; d < K; ++d) {
+          float pv[DIM];
+          probe_values<N, DIM>(p, dir0 + (d < ndir ? d : 0), wid, nodei[T], pv);
+          if (hh == 0) {
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) vtab[d * C::POS_F + col[T] * DIM + k] = (valid[T] && d < ndir) ? pv[k] : 0.f;
+          }
+        }
+      }
+      wave_lds_fence();
+      if (lane < G * K) {
+        const int w = lane / K, d = lane - w * K;
+        if (w < nwalk && d < ndir && (!p.repair || p.mark[walker0 + w] != 0)) {
+          const float hv = p.h[walker0 + w];
+          const float op = 1.0f + hv, rs = 1.0f / sqrtf(op);
+          p.q_out[(long long)(dir0 + d) * p.B + walker0 + w] =
+              probe_quadratic_form<N, DIM, C::POS_F>(dscr, vtab, w, d, 1.0f / op, sqrtf(hv) * rs);
+        }
+      }
+      wave_lds_fence();
+    } else {
     wave_lds_fence();
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
@@ -381,6 +470,7 @@ __global__ void __launch_bounds__(WAVES * 64, 1) egnn_div_kernel(DivParams p) {
         }
     }
     wave_lds_fence();
+    }
     if (p.out && ch == 0) {  // primal denoiser D = c_s x + c_out (F - mean F), F = pos^L - pos^0 (x = pos^0 / c_in)
       float* scr = PB;
 #pragma unroll
@@ -498,9 +588,12 @@ __device__ __forceinline__ void silu_dsilu16(const f32x16& vin, float pre, f32x1
   }
 }
 
-template <int N, int DIM, int G, int WAVES, int K, int DAL, int OCC = 1>
+// (MODE: as in egnn_div_kernel)
+template <int N, int DIM, int G, int WAVES, int K, int DAL, int OCC = 1, typename... MODE>
 __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParams p) {
+  constexpr bool PROBE = sizeof...(MODE) > 0;
   using C = DivCfg<N, DIM, G, WAVES, K, DAL>;
+  static_assert(!PROBE || (K > 0 && G * K <= 64), "probe read-out: one lane per (walker, probe slot)");
   constexpr int NT = C::NT;
   constexpr int KA = K > 0 ? K : 1;  // array extents (K = 0, the cache writer: no direction, the loops over d vanish)
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -553,6 +646,11 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParam
       c_in[T] = rs;
       c_out[T] = sqrtf(hv) * rs;
       const float tfeat = 0.125f * logf(hv);
+      [[maybe_unused]] float pv[PROBE ? KA : 1][DIM];
+      if constexpr (PROBE) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) probe_values<N, DIM>(p, p.dir0 + (q < p.ndir ? q : 0), wid, nodei[T], pv[q]);
+      }
 #pragma unroll
       for (int k = 0; k < DIM; ++k) {
         const long long gi = (walker0 * N + col[T]) * DIM + k;
@@ -565,7 +663,9 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParam
         }
 #pragma unroll
         for (int q = 0; q < K; ++q) {
-          const float v = (valid[T] && q < p.ndir && nodei[T] * DIM + k == p.dir0 + q) ? 1.0f : 0.f;  // unit direction
+          float v;  // unit direction, or the probe at its true scale
+          if constexpr (PROBE) v = (valid[T] && q < p.ndir) ? pv[q][k] : 0.f;
+          else v = (valid[T] && q < p.ndir && nodei[T] * DIM + k == p.dir0 + q) ? 1.0f : 0.f;
           dposi[T][q][k] = v;
           dp0i[T][q][k] = v;
           if (hh == 0) {
@@ -908,6 +1008,20 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParam
           if (hh == 0) dscr[d * C::POS_F + col[T] * DIM + k] = dposi[T][d][k];
         }
     if (lane < G * K) tsl[lane] = 0.f;
+    if constexpr (PROBE) {
+      // the terms are the quadratic forms <v, dD>, dD = c_s v + c_out c_in (dF - mean dF): the seed table still holds the
+      // probes at their true scale; one lane per (walker, probe slot) sums in a fixed order
+      const float* vtab = dpos0;  // [K][NCOLP*DIM]
+      wave_lds_fence();
+      if (lane < G * K) {
+        const int w = lane / KA, d = lane - w * KA;
+        if (w < nwalk && d < p.ndir) {
+          const float hv = p.h[walker0 + w];
+          const float op = 1.0f + hv, rs = 1.0f / sqrtf(op);
+          tsl[lane] = probe_quadratic_form<N, DIM, C::POS_F>(dscr, vtab, w, d, 1.0f / op, (sqrtf(hv) * rs) * rs);
+        }
+      }
+    } else {
     wave_lds_fence();
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
@@ -923,6 +1037,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParam
           tsl[(col[T] / N) * K + d] = fmaf(c_out[T] * c_in[T], dF, c_s[T]);
         }
     }
+    }
     wave_lds_fence();
     bool bad[NT];
 #pragma unroll
@@ -935,7 +1050,14 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_div_fast_kernel(DivParam
         for (int d = 0; d < K; ++d) sum += tsl[(valid[T] ? w : 0) * K + d];
         bad[T] = valid[T] && !__builtin_isfinite(sum);
         if (valid[T] && hh == 0 && nodei[T] == 0) {
-          if (!bad[T]) p.diag_acc[walker0 + w] += sum;
+          if constexpr (PROBE) {
+            if (!bad[T])
+#pragma unroll
+              for (int d = 0; d < K; ++d)
+                if (d < p.ndir) p.q_out[(long long)(p.dir0 + d) * p.B + walker0 + w] = tsl[w * K + d];
+          } else {
+            if (!bad[T]) p.diag_acc[walker0 + w] += sum;
+          }
           p.mark[walker0 + w] = bad[T] ? 1 : 0;
           if (bad[T] && p.bad_flag) *p.bad_flag = p.bad_seq;
         }
@@ -2186,6 +2308,7 @@ struct DivSystem {
   DivKernel writer;            // nullable: cache writer, the first launch of a trace streamed by the block-shared kernel
   DivKernel shared, owned;     // nullable: tangent-only kernels (primal cache), block-shared and wave-owned
   size_t (*group_f)(int);      // cache floats per walker group
+  DivKernel bf16x3_probe, f16_probe;  // the first two with probes for tangent inputs (pita_egnn_trace_probes)
 };
 template <int N, int DIM, int G, int WAVES, int K, int DAL>
 static size_t div_lds_bytes_of(int L) { return DivCfg<N, DIM, G, WAVES, K, DAL>::lds_bytes(L); }
@@ -2216,6 +2339,8 @@ static DivSystem div_system() {
               {egnn_div_kernel<N, DIM, G, WAVES, K>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K},
               {egnn_div_fast_kernel<N, DIM, G, WAVES, K, 1>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K},
               {}, {}, {}, divcache_group_f<N, DIM, G>};
+  s.bf16x3_probe = {egnn_div_kernel<N, DIM, G, WAVES, K, DivProbes>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K};
+  s.f16_probe = {egnn_div_fast_kernel<N, DIM, G, WAVES, K, 1, 1, DivProbes>, div_lds_bytes_of<N, DIM, G, WAVES, K, 1>, WAVES, K};
   if constexpr (WRITER)
     s.writer = {egnn_div_fast_kernel<N, DIM, G, WAVES, 0, 0, 1>, div_lds_bytes_of<N, DIM, G, WAVES, 0, 0>, WAVES, 0};
   if constexpr (SHR_K > 0)
@@ -2324,6 +2449,16 @@ static int ensure_marks(pita_egnn_t* net, size_t B, hipStream_t st) {
   PITA_HIP_CHECK(grow_scratch(net->d_mark, net->mark_bytes, sizeof(int) * B, st, 64));
   PITA_HIP_CHECK(hipMemsetAsync(net->d_mark + B, 0, 64, st));
   return PITA_OK;
+}
+
+// est[b] = (sum over the K probes, in probe order from +0, of q[k * B + b]) / (float)K
+__global__ void __launch_bounds__(256) egnn_probe_mean_kernel(const float* __restrict__ q, float* __restrict__ est,
+                                                              long long B, int K) {
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.0f;
+  for (int k = 0; k < K; ++k) s += q[(long long)k * B + b];
+  est[b] = s / (float)K;
 }
 
 }  // namespace pita
@@ -2535,5 +2670,65 @@ extern "C" int pita_egnn_jacobian_trace(pita_egnn_t* net, const float* h, const 
       if (rc != PITA_OK) return rc;
     }
   }
+  return PITA_OK;
+}
+
+// Hutchinson estimate of trace(J_x D) on the hidden-32 EGNN: the probes go through the multi-direction kernels K_launch =
+// pita_egnn_div_directions at a time, so the probes of a launch share ONE primal evaluation (a short last launch is
+// allowed); each launch stores its quadratic forms <v_k, J_x D v_k> in [n_probes, B] -- per_probe when the caller gave
+// one, else a handle-owned buffer -- and one reduction forms the mean in probe order.  Precision-2 handles: the f16
+// kernel, which leaves the probes of a walker with a non-finite term unwritten and marks it, then the bf16x3 kernel on
+// exactly the marked walkers (marks, flag word and early exit as in pita_egnn_div_accumulate)
+extern "C" int pita_egnn_trace_probes(pita_egnn_t* net, const float* h, const float* x, const float* beta, int n_probes,
+                                      const float* probes, uint64_t seed, uint64_t walker_offset, int64_t step,
+                                      float* estimate, float* per_probe, float* denoiser_out, int64_t B, void* stream) {
+  PITA_REQUIRE(net && B >= 0, "pita_egnn_trace_probes: bad argument");
+  PITA_REQUIRE(n_probes >= 1, "pita_egnn_trace_probes: n_probes must be at least 1");
+  PITA_REQUIRE(probes || n_probes <= kMaxDrawnProbes, "pita_egnn_trace_probes: probes drawn in the kernel need n_probes <= %d",
+               kMaxDrawnProbes);
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(h && x && estimate, "pita_egnn_trace_probes: null argument");
+  PITA_REQUIRE(beta || net->cfg.in_node_nf == 1, "pita_egnn_trace_probes: beta required for in_node_nf=2");
+  const DivPlan pl = div_plan(net);
+  if (!pl.sys) return fail(PITA_EUNSUPPORTED, "pita_egnn_trace_probes: no kernel for this particle system");
+  const DivSystem& s = *pl.sys;
+  PITA_REQUIRE((long long)n_probes * B < (1LL << 40), "pita_egnn_trace_probes: too many (probe, walker) pairs");
+  PitaDeviceGuard guard(net->device);
+  hipStream_t st = (hipStream_t)stream;
+  float* q = per_probe;
+  if (!q) {
+    PITA_HIP_CHECK(grow_scratch(net->d_probe_q, net->probe_q_bytes, sizeof(float) * (size_t)n_probes * (size_t)B, st));
+    q = net->d_probe_q;
+  }
+  DivParams p = div_params(net);
+  p.B = B; p.h = h; p.x = x; p.beta = beta; p.q_out = q;
+  p.probes = probes; p.seed = seed; p.walker_offset = walker_offset; p.step = step;
+  if (pl.f16) {
+    const int rc = ensure_marks(net, (size_t)B, st);
+    if (rc != PITA_OK) return rc;
+    p.mark = net->d_mark;
+    p.bad_flag = net->d_mark + net->mark_bytes / sizeof(int);
+  }
+  const long long grid = div_grid(net, s, B).grid;
+  for (int k0 = 0; k0 < n_probes; k0 += s.K) {
+    p.dir0 = k0;
+    p.ndir = (n_probes - k0) < s.K ? (n_probes - k0) : s.K;
+    p.out = k0 == 0 ? denoiser_out : nullptr;
+    p.repair = 0;
+    int rc;
+    if (!pl.f16) {
+      rc = div_launch(s.bf16x3_probe, grid, p, st);
+    } else {
+      p.bad_seq = ++net->div_seq;
+      rc = div_launch(s.f16_probe, grid, p, st);
+      if (rc != PITA_OK) return rc;
+      p.repair = 1;
+      rc = div_launch(s.bf16x3_probe, grid, p, st);
+    }
+    if (rc != PITA_OK) return rc;
+  }
+  hipLaunchKernelGGL(egnn_probe_mean_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, q, estimate, (long long)B,
+                     n_probes);
+  PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

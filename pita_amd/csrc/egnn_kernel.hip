@@ -611,6 +611,9 @@ extern "C" int pita_egnn_create(pita_egnn_t** out, const pita_egnn_config* cfg, 
     if (s.n == cfg->n_particles && s.dim == cfg->n_dim) shape = &s;
   for (const auto& s : kShapesSmall)
     if (s.n == cfg->n_particles && s.dim == cfg->n_dim) shape_small = &s;
+  if (!shape)  // (before anything is allocated: the LDS opt-in below reads the shape)
+    return fail(PITA_EUNSUPPORTED, "pita_egnn_create: no kernel for %d particles in %d dimensions", cfg->n_particles,
+                cfg->n_dim);
   const int H = EH, L = cfg->n_layers, nf = cfg->in_node_nf;
   const size_t n_mats = (size_t)L * M_COUNT * MAT_F, n_vecs = VEC_EMB_F + (size_t)L * VEC_LAYER_F;
   float* h_mats = new float[n_mats];
@@ -854,6 +857,7 @@ extern "C" int pita_egnn_destroy(pita_egnn_t* net) {
   (void)hipFree(net->d_bk);
   (void)hipFree(net->d_mark);
   (void)hipFree(net->d_divcache);
+  (void)hipFree(net->d_probe_q);
   delete net;
   return PITA_OK;
 }

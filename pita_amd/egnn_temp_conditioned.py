@@ -201,6 +201,49 @@ class EGNN_dynamics(nn.Module):
                        "pita_egnn_jacobian_trace")
         return (trace, den) if want_denoiser else trace
 
+    def trace_probes(self, h_t, x_t, beta, n_probes, probes=None, seed=0, walker_offset=0, step=0, want_denoiser=False,
+                     want_per_probe=False):
+        """(estimate, D or None, per_probe or None): the Hutchinson estimate of trace(J_x D_theta(h, x)) per walker from
+        ``n_probes`` probes, mean_k <v_k, J_x D v_k>, in ONE call (pita_egnn_trace_probes): the probes go through the
+        multi-direction kernels of ``jacobian_trace`` in the place of unit vectors, so the probes of a launch share one
+        primal evaluation, on the handle's own arithmetic.  ``probes`` [K, B, n*d]: the tangent inputs (parity hook);
+        None: Rademacher signs drawn in the kernel, keyed (seed, walker_offset + row, step) -- what
+        ``pita_amd.utils.rademacher_probes`` returns for the same key (K <= 256).  ``want_per_probe``: also the [K, B]
+        quadratic forms.  Returns None when the particle system has no multi-direction kernel (PITA_EUNSUPPORTED): the
+        caller takes ``n_probes`` ``jvp`` launches.  ``VEReverseSDE(divergence="hutchinson", shared_primal=True)``
+        takes it."""
+        x_t = _lib.dev_tensor(x_t, "x_t")
+        B = x_t.shape[0]
+        K = int(n_probes)
+        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
+        b = None
+        if self.condition_temperature:
+            if beta is None:
+                raise ValueError("EGNN_dynamics(condition_temperature=True) needs beta")
+            b = _as_batch(beta, B, x_t.device)
+        if probes is not None:
+            probes = _lib.dev_tensor(probes, "probes")
+            if tuple(probes.shape) != (K, B, x_t.shape[1]):
+                raise ValueError(f"probes has shape {tuple(probes.shape)}, expected {(K, B, x_t.shape[1])}")
+        est = torch.empty(B, device=x_t.device)
+        den = torch.empty_like(x_t) if want_denoiser else None
+        per = torch.empty(max(K, 0), B, device=x_t.device) if want_per_probe else None
+        try:
+            net = self._native(x_t.device)
+        except _lib.PitaHipError as e:
+            if getattr(e, "code", 0) == -2:  # PITA_EUNSUPPORTED: the library has no kernel at all for this system
+                return None
+            raise
+        with torch.cuda.device(x_t.device):
+            rc = _lib.lib().pita_egnn_trace_probes(
+                net, h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b), K, _lib.ptr(probes),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step), est.data_ptr(), _lib.ptr(per), _lib.ptr(den),
+                B, _lib.stream_ptr(x_t.device))
+        if rc == -2:  # PITA_EUNSUPPORTED
+            return None
+        _lib.check(rc, "pita_egnn_trace_probes")
+        return est, den, per
+
     vjp_h_parts = True  # vjp(..., want_h_parts=True) is available
 
     def vjp(self, h_t, x_t, beta, cot=None, want_primal=True, want_dot_h=False, want_h_parts=False):

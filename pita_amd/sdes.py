@@ -19,6 +19,8 @@
   ``VEReverseSDE(divergence="hutchinson", n_probes=K)`` replaces the exact trace by the Hutchinson estimate the
   reference's utils.py ships beside ``compute_divergence_exact``: mean over K Rademacher probes of <v, J_x D v>
   (``jacobian_trace_estimate`` on the wide EGNN: pita_egnn_wide_trace_probes, one call; K ``jvp`` launches elsewhere).
+  ``shared_primal=True`` sends the probes of the hidden-32 EGNN through ``trace_probes`` (pita_egnn_trace_probes: the
+  multi-direction kernels of the exact trace, probes in the place of unit vectors) instead of the K ``jvp`` launches.
   The log-weight drift then carries zero-mean estimator noise; the default stays exact.
 """
 from dataclasses import dataclass
@@ -108,10 +110,19 @@ def _per_walker(t, x):
 
 class VEReverseSDE:
     def __init__(self, noise_schedule, energy_net=None, score_net=None, cdf=None, pin_energy=False,
-                 debias_inference=True, divergence="exact", n_probes=None):
+                 debias_inference=True, divergence="exact", n_probes=None, shared_primal=False):
         """``divergence`` (extension): "exact" -- trace(J_x D) over all n*d unit directions, the default -- or
         "hutchinson" -- its unbiased estimate from ``n_probes`` >= 1 Rademacher probes (utils.py's estimator), drawn
-        per (probe_key of ``f``, global walker index): n_probes / (n*d) of the exact trace's work."""
+        per (probe_key of ``f``, global walker index): n_probes / (n*d) of the exact trace's work.
+        ``shared_primal`` (extension, with "hutchinson"): a backbone with ``trace_probes`` (the hidden-32 EGNN) takes it
+        -- one call whose probes share the primal evaluation, on the handle's own arithmetic -- instead of n_probes
+        ``jvp`` launches; where it answers None the ``jvp`` launches run.  The default False keeps every bit of the
+        ``jvp`` path; backbones with ``jacobian_trace_estimate`` ignore the flag."""
+        if not isinstance(shared_primal, bool):
+            raise ValueError(f"shared_primal must be a bool, got {shared_primal!r}")
+        if shared_primal and divergence != "hutchinson":
+            raise ValueError("shared_primal=True needs divergence='hutchinson'")
+        self.shared_primal = shared_primal
         if divergence not in ("exact", "hutchinson"):
             raise ValueError(f"divergence must be 'exact' or 'hutchinson', got {divergence!r}")
         if divergence == "hutchinson":
@@ -204,7 +215,8 @@ class VEReverseSDE:
         """D and trace(J_x D) of the score net's denoiser from the multi-direction divergence kernel (dim / K launches;
         D is a by-product of the first one); backbones without it use dim single-direction JVP launches.
         ``divergence="hutchinson"``: the Hutchinson estimate in the trace's place -- the backbone's one-call
-        ``jacobian_trace_estimate`` where it has one, else n_probes ``jvp(vx=v_k)`` launches on probes drawn by
+        ``jacobian_trace_estimate`` where it has one, under ``shared_primal`` its ``trace_probes``, else n_probes
+        ``jvp(vx=v_k)`` launches on probes drawn by
         ``rademacher_probes`` and the mean of the <v_k, dD_k>, formed on the device in probe order."""
         if self.divergence == "hutchinson":
             seed, off, step = probe_key
@@ -213,6 +225,10 @@ class VEReverseSDE:
                 est, D_S, _ = model.jacobian_trace_estimate(ht, x, beta, K, seed=seed, walker_offset=off, step=step,
                                                             want_denoiser=True)
                 return D_S, est
+            if self.shared_primal and hasattr(model, "trace_probes"):
+                res = model.trace_probes(ht, x, beta, K, seed=seed, walker_offset=off, step=step, want_denoiser=True)
+                if res is not None:
+                    return res[1], res[0]
             if not hasattr(model, "jvp"):
                 raise NotImplementedError(
                     "debias_inference=True needs a backbone with a forward-mode derivative (jvp: the HIP EGNN and MLP backbones)")

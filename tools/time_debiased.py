@@ -1,5 +1,7 @@
 """Timing of the debiased (Feynman-Kac) regime: walker-steps/s of sde.f at a given batch and particle count.
-    python tools/time_debiased.py [walkers = 8192] [particles = 13]
+    python tools/time_debiased.py [walkers = 8192] [particles = 13] [--probes K[,K...]]
+--probes: also the step under divergence="hutchinson" at each K, K jvp launches against shared_primal=True
+(pita_egnn_trace_probes), alternating, median of 7 (tools/time_egnn_trace_probes.py --step prints the same with checksums)
     rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python3 tools/time_debiased.py 32768 55"""
 import copy, os, sys, time
 import numpy as np, torch
@@ -7,6 +9,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import pita_amd
 from pita_amd.energy_net import EnergyNet
+PROBES = []
+if "--probes" in sys.argv:
+    i = sys.argv.index("--probes")
+    PROBES = [int(k) for k in sys.argv[i + 1].split(",")]
+    del sys.argv[i:i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 NP = int(sys.argv[2]) if len(sys.argv) > 2 else 13
 w = dict(np.load(os.path.join(ROOT, "tests/golden/egnn_weights_trainedlike.npz")))
@@ -41,3 +48,19 @@ t0 = time.perf_counter()
 for k in range(3): net.jacobian_trace(h1, x, b1)
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 3
 print(f"jacobian_trace ({3 * NP} directions): {dt*1e3:.2f} ms")
+
+import statistics
+for K in PROBES:
+    mk = lambda **kw: pita_amd.VEReverseSDE(noise_schedule=sched, score_net=pita_amd.ScoreNet(net), debias_inference=True,
+                                            energy_net=EnergyNet(copy.deepcopy(net)), divergence="hutchinson", n_probes=K, **kw)
+    paths = {"K x jvp": mk(), "shared_primal": mk(shared_primal=True)}
+    times = {k: [] for k in paths}
+    for rep in range(9):  # two warm-up repetitions, seven timed, alternating
+        for k, s_ in paths.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); terms = s_.f(t, x, 1.0, gam, None, None, probe_key=(11, 0, 5)); e1.record()
+            e1.synchronize()
+            if rep >= 2: times[k].append(e0.elapsed_time(e1))
+    print(f"debiased f, hutchinson K={K}: " + ", ".join(f"{k} median {statistics.median(v):.2f} ms (min {min(v):.2f}, max {max(v):.2f})"
+                                                       for k, v in times.items())
+          + f"; checksum {float(terms.drift_A.double().sum()):.9e} nonfinite {int((~torch.isfinite(terms.drift_A)).sum())}")
