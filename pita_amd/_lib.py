@@ -152,6 +152,12 @@ _PROTOS = {
     "pita_systematic_resample": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
     "pita_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "pita_count_runs": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "pita_logweight_stats_workspace_bytes": (c_size_t, [c_int64]),
+    "pita_logweight_stats": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "pita_adaptive_resample_workspace_bytes": (c_size_t, [c_int64]),
+    "pita_adaptive_resample": (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "pita_adaptive_resample_single_launch": (c_int, [c_int64]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -307,69 +307,67 @@ constexpr int RS_T = 256, RS_E = 1024;  // threads and elements per block
 
 __device__ __forceinline__ float rs_exp(float v) { return (float)exp((double)v); }
 
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
+// The arithmetic of the passes lives in the rs_pass_* device functions of (virtual block vb of RS_E elements, thread t of
+// RS_T): the multi-block kernels run one virtual block per block (vb = blockIdx.x, t = threadIdx.x), the one-launch kernel
+// of the adaptive event (adaptive_resample_block_kernel) runs all of them in ONE block of four groups of RS_T threads.  The
+// summation order -- and with it every bit of the ids -- is theirs alone.  Functions with a barrier are called by every
+// thread of the block (a virtual block past the end loads nothing and contributes nothing).
+__device__ __forceinline__ double block_sum_d(double v, double* red, int t) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  if ((t & 63) == 0) red[t >> 6] = v;
   __syncthreads();
   double r = 0.0;
   for (int k = 0; k < RS_T / 64; ++k) r += red[k];
   return r;
 }
 
-__global__ void __launch_bounds__(RS_T) rs_max_kernel(const float* __restrict__ logits, long long B, float* __restrict__ bmax) {
-  __shared__ float red[RS_T / 64];
-  const long long lo = (long long)blockIdx.x * RS_E;
+// pass A: the maximum of virtual block vb (valid in t == 0); red: RS_T / 64 slots of the virtual block
+__device__ __forceinline__ float rs_pass_max(const float* logits, long long B, long long vb, int t, float* red) {
+  const long long lo = vb * RS_E;
   float mx = -INFINITY;
-  for (int i = threadIdx.x; i < RS_E; i += RS_T)
+  for (int i = t; i < RS_E; i += RS_T)
     if (lo + i < B) mx = fmaxf(mx, logits[lo + i]);
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  if ((t & 63) == 0) red[t >> 6] = mx;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (t == 0)
     for (int k = 1; k < RS_T / 64; ++k) mx = fmaxf(mx, red[k]);
-    bmax[blockIdx.x] = mx;
-  }
+  return mx;
 }
 
-// phase 0: sums of exp(l - max);  phase 1: sums of the clipped weights
-__global__ void __launch_bounds__(RS_T) rs_sum_kernel(const float* __restrict__ logits, long long B, int nblk,
-                                                      const float* __restrict__ bmax, const double* __restrict__ bsum,
-                                                      double* __restrict__ out, int phase) {
-  __shared__ double red[RS_T / 64];
+// the global maximum and the softmax denominator (rounded to fp32 once) from the blocks' partials, in index order
+__device__ __forceinline__ float rs_fold_max(const float* bmax, int nblk) {
   float mx = -INFINITY;
   for (int k = 0; k < nblk; ++k) mx = fmaxf(mx, bmax[k]);
-  float sm = 1.0f;
-  if (phase == 1) {
-    double t = 0.0;
-    for (int k = 0; k < nblk; ++k) t += bsum[k];
-    sm = (float)t;
-  }
-  const long long lo = (long long)blockIdx.x * RS_E;
+  return mx;
+}
+__device__ __forceinline__ double rs_fold_sum(const double* v, int nblk) {
+  double t = 0.0;
+  for (int k = 0; k < nblk; ++k) t += v[k];
+  return t;
+}
+
+// passes B (phase 0: exp(l - max)) and C (phase 1: the clipped weights): the sum over virtual block vb, in every thread
+__device__ __forceinline__ double rs_pass_sum(const float* logits, long long B, long long vb, int t, float mx, float sm,
+                                              int phase, double* red) {
+  const long long lo = vb * RS_E;
   double acc = 0.0;
-  for (int i = threadIdx.x; i < RS_E; i += RS_T)
+  for (int i = t; i < RS_E; i += RS_T)
     if (lo + i < B) {
       float w = rs_exp(logits[lo + i] - mx);
       if (phase == 1) w = fminf(fmaxf(w / sm, 1e-6f), 1.0f);
       acc += (double)w;
     }
-  acc = block_sum_d(acc, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = acc;
+  return block_sum_d(acc, red, t);
 }
 
-__global__ void __launch_bounds__(RS_T) rs_bins_kernel(const float* __restrict__ logits, long long B, int nblk,
-                                                       const float* __restrict__ bmax, const double* __restrict__ bsum,
-                                                       const double* __restrict__ bw, float* __restrict__ bins) {
-  __shared__ double part[RS_T];
-  float mx = -INFINITY;
-  for (int k = 0; k < nblk; ++k) mx = fmaxf(mx, bmax[k]);
-  double t = 0.0;
-  for (int k = 0; k < nblk; ++k) t += bsum[k];
-  const float sm = (float)t;
-  double base = 0.0;
-  for (int k = 0; k < (int)blockIdx.x; ++k) base += bw[k];
+// pass D: the bins of virtual block vb on top of `base`, the sum of the earlier blocks' totals; part: RS_T slots.  Every
+// thread reads its own elements before it writes them: `bins` may be `logits` (the one-launch kernel scans in place).
+__device__ __forceinline__ void rs_pass_bins(const float* logits, long long B, long long vb, int t, float mx, float sm,
+                                             double base, double* part, float* bins) {
   constexpr int PER = RS_E / RS_T;  // contiguous elements per thread
-  const long long lo = (long long)blockIdx.x * RS_E + (long long)threadIdx.x * PER;
+  const long long lo = vb * RS_E + (long long)t * PER;
   float w[PER];
   double acc = 0.0;
 #pragma unroll
@@ -377,14 +375,14 @@ __global__ void __launch_bounds__(RS_T) rs_bins_kernel(const float* __restrict__
     w[q] = (lo + q < B) ? fminf(fmaxf(rs_exp(logits[lo + q] - mx) / sm, 1e-6f), 1.0f) : 0.0f;
     acc += (double)w[q];
   }
-  part[threadIdx.x] = acc;
+  part[t] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (t == 0) {
     double run = 0.0;
     for (int k = 0; k < RS_T; ++k) { const double v = part[k]; part[k] = run; run += v; }
   }
   __syncthreads();
-  acc = base + part[threadIdx.x];
+  acc = base + part[t];
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     acc += (double)w[q];
@@ -392,19 +390,65 @@ __global__ void __launch_bounds__(RS_T) rs_bins_kernel(const float* __restrict__
   }
 }
 
+// pass E for walker k: u_k = (u0 + fp32(k * fp32(1/B))) mod 1 in double; id = #bins < u  (digitize right=True), clamp
+__device__ __forceinline__ long long rs_search(const float* bins, long long B, double u0, float invB, long long k) {
+  const double u = fmod(u0 + (double)((float)k * invB), 1.0);
+  long long a = 0, b = B;  // first index with bins[idx] >= u
+  while (a < b) {
+    const long long m = (a + b) >> 1;
+    if ((double)bins[m] < u) a = m + 1; else b = m;
+  }
+  return (a >= B) ? B - 1 : a;
+}
+
+// one block's share of each multi-block pass: the body of the plain kernel and, behind the device flag, of the gated one
+__device__ __forceinline__ void rs_max_block(const float* logits, long long B, float* bmax) {
+  __shared__ float red[RS_T / 64];
+  const float mx = rs_pass_max(logits, B, blockIdx.x, threadIdx.x, red);
+  if (threadIdx.x == 0) bmax[blockIdx.x] = mx;
+}
+__device__ __forceinline__ void rs_sum_block(const float* logits, long long B, int nblk, const float* bmax,
+                                             const double* bsum, double* out, int phase) {
+  __shared__ double red[RS_T / 64];
+  const float mx = rs_fold_max(bmax, nblk);
+  const float sm = phase == 1 ? (float)rs_fold_sum(bsum, nblk) : 1.0f;
+  const double acc = rs_pass_sum(logits, B, blockIdx.x, threadIdx.x, mx, sm, phase, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+__device__ __forceinline__ void rs_bins_block(const float* logits, long long B, int nblk, const float* bmax,
+                                              const double* bsum, const double* bw, float* bins) {
+  __shared__ double part[RS_T];
+  const float mx = rs_fold_max(bmax, nblk);
+  const float sm = (float)rs_fold_sum(bsum, nblk);
+  const double base = rs_fold_sum(bw, (int)blockIdx.x);
+  rs_pass_bins(logits, B, blockIdx.x, threadIdx.x, mx, sm, base, part, bins);
+}
+__device__ __forceinline__ void rs_search_grid(const float* bins, long long B, double u0, long long* ids) {
+  const float invB = (float)(1.0 / (double)B);
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < B; k += (long long)gridDim.x * 256)
+    ids[k] = rs_search(bins, B, u0, invB, k);
+}
+
+__global__ void __launch_bounds__(RS_T) rs_max_kernel(const float* __restrict__ logits, long long B, float* __restrict__ bmax) {
+  rs_max_block(logits, B, bmax);
+}
+
+// phase 0: sums of exp(l - max);  phase 1: sums of the clipped weights
+__global__ void __launch_bounds__(RS_T) rs_sum_kernel(const float* __restrict__ logits, long long B, int nblk,
+                                                      const float* __restrict__ bmax, const double* __restrict__ bsum,
+                                                      double* __restrict__ out, int phase) {
+  rs_sum_block(logits, B, nblk, bmax, bsum, out, phase);
+}
+
+__global__ void __launch_bounds__(RS_T) rs_bins_kernel(const float* __restrict__ logits, long long B, int nblk,
+                                                       const float* __restrict__ bmax, const double* __restrict__ bsum,
+                                                       const double* __restrict__ bw, float* __restrict__ bins) {
+  rs_bins_block(logits, B, nblk, bmax, bsum, bw, bins);
+}
+
 __global__ void __launch_bounds__(256) rs_search_kernel(const float* __restrict__ bins, long long B, double u0,
                                                         long long* __restrict__ ids) {
-  // u_k = (u0 + fp32(k * fp32(1/B))) mod 1 in double; ids = #bins < u  (digitize right=True), clamp
-  const float invB = (float)(1.0 / (double)B);
-  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < B; k += (long long)gridDim.x * 256) {
-    const double u = fmod(u0 + (double)((float)k * invB), 1.0);
-    long long a = 0, b = B;  // first index with bins[idx] >= u
-    while (a < b) {
-      const long long m = (a + b) >> 1;
-      if ((double)bins[m] < u) a = m + 1; else b = m;
-    }
-    ids[k] = (a >= B) ? B - 1 : a;
-  }
+  rs_search_grid(bins, B, u0, ids);
 }
 
 __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restrict__ src, const long long* __restrict__ ids,
@@ -418,8 +462,8 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restric
 
 // distinct parents of a systematic resampling = cyclic runs of the id vector (ids are non-decreasing up to the rotation by the
 // event's uniform): one block, integer sums -- replaces roll + != + cast + sum + clamp (five launches) behind every event
-__global__ void __launch_bounds__(1024) count_runs_kernel(const long long* __restrict__ ids, long long B,
-                                                          long long* __restrict__ out) {
+template <class Id>
+__device__ __forceinline__ void count_runs_block(const Id* ids, long long B, long long* out) {
   __shared__ unsigned part[16];
   unsigned c = 0;
   for (long long i = threadIdx.x; i < B; i += 1024) c += ids[i] != ids[i == 0 ? B - 1 : i - 1] ? 1u : 0u;
@@ -431,6 +475,192 @@ __global__ void __launch_bounds__(1024) count_runs_kernel(const long long* __res
     unsigned t = 0;
     for (int w = 0; w < 16; ++w) t += part[w];
     *out = t < 1u ? 1 : (long long)t;
+  }
+}
+
+__global__ void __launch_bounds__(1024) count_runs_kernel(const long long* __restrict__ ids, long long B,
+                                                          long long* __restrict__ out) {
+  count_runs_block(ids, B, out);
+}
+
+// ---------------------------------------------------------------------------- adaptive resampling event
+// Statistics of B log-weights a (pita_hip.h: pita_logweight_stats) by ONE block of AR_T threads, and the decision of an
+// adaptive event from them.  Fixed order: thread t takes a[t], a[t + AR_T], ... in double, xor-shuffle wave reduction,
+// the sixteen wave partials added in index order -- the same in the stats kernel (a in global memory) and in the
+// one-launch event (a in LDS), so both write the same bits.  Two sweeps: the maximum of the finite entries and the
+// counts, then sum w and sum w^2 of w = exp(a - max), differences and exp in double.  NaN and +inf entries are counted
+// and left out of every sum (and force the event); -inf entries are counted and contribute 0.
+constexpr int AR_T = 1024, AR_W = AR_T / 64;
+
+struct StatsLds {
+  double s1[AR_W], s2[AR_W];
+  float mx[AR_W];
+  unsigned bad[AR_W], ninf[AR_W];
+};
+
+// returns the decision (identical in every thread); thread 0 writes stats[6].  Called by all AR_T threads.
+__device__ __forceinline__ int logweight_stats_block(const float* a, long long B, double theta, double* stats,
+                                                     StatsLds& L) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  float mx = -INFINITY;
+  unsigned bad = 0, ninf = 0;
+  for (long long i = t; i < B; i += AR_T) {
+    const float v = a[i];
+    if (v != v || v == INFINITY) ++bad;
+    else if (v == -INFINITY) ++ninf;
+    else mx = fmaxf(mx, v);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    bad += __shfl_xor(bad, o, 64);
+    ninf += __shfl_xor(ninf, o, 64);
+  }
+  if (lane == 0) { L.mx[wv] = mx; L.bad[wv] = bad; L.ninf[wv] = ninf; }
+  __syncthreads();
+  mx = -INFINITY; bad = 0; ninf = 0;
+  for (int k = 0; k < AR_W; ++k) { mx = fmaxf(mx, L.mx[k]); bad += L.bad[k]; ninf += L.ninf[k]; }
+  const double m = mx > -INFINITY ? (double)mx : 0.0;  // no finite entry: 0
+
+  double s1 = 0.0, s2 = 0.0;
+  for (long long i = t; i < B; i += AR_T) {
+    const float v = a[i];
+    if (v == v && fabsf(v) != INFINITY) {
+      const double w = exp((double)v - m);
+      s1 += w;
+      s2 = fma(w, w, s2);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    s1 += __shfl_xor(s1, o, 64);
+    s2 += __shfl_xor(s2, o, 64);
+  }
+  if (lane == 0) { L.s1[wv] = s1; L.s2[wv] = s2; }
+  __syncthreads();
+  s1 = 0.0; s2 = 0.0;
+  for (int k = 0; k < AR_W; ++k) { s1 += L.s1[k]; s2 += L.s2[k]; }
+  const double ess = (s1 > 0.0 && s1 < (double)INFINITY) ? s1 * s1 / s2 : 0.0;
+  if (t == 0) {
+    stats[0] = m;
+    stats[1] = m + log(s1 / (double)B);
+    stats[2] = ess;
+    stats[3] = ess / (double)B;
+    stats[4] = (double)bad;
+    stats[5] = (double)ninf;
+  }
+  return (theta >= 1.0 || bad > 0u || ess <= theta * (double)B) ? 1 : 0;
+}
+
+// the statistics as a pass of their own: pita_logweight_stats (resampled == nullptr) and the first pass of the gated event
+__global__ void __launch_bounds__(AR_T) logweight_stats_kernel(const float* __restrict__ a, long long B, double theta,
+                                                               double* __restrict__ stats, int* __restrict__ resampled) {
+  __shared__ StatsLds L;
+  const int flag = logweight_stats_block(a, B, theta, stats, L);
+  if (threadIdx.x == 0 && resampled) *resampled = flag;
+}
+
+// One adaptive event of B <= AR_MAX_B walkers in ONE launch: the log-weights are read once into LDS, the block takes
+// the statistics and the decision, and, where the event resamples, the five passes of pita_systematic_resample and the
+// run count without leaving the block.  The four groups of RS_T threads each take one virtual block of RS_E walkers per
+// round through the rs_pass_* functions, so every sum has the order of the multi-block kernels and the ids are theirs bit
+// for bit.  The bins overwrite the log-weights in place; the parents are kept as 16-bit words (ids < 65 536) for the run
+// count.  Dynamic LDS: float val[B] | unsigned short par[B].
+// AR_MAX_B is where the launch still wins: measured against the seven launches of the fixed sequence it takes 0.93 of
+// their time at 2 048 walkers and 3.2 times it at 16 384 (profiles/r14_adaptive_resample.txt) -- one compute unit then
+// walks sixteen virtual blocks, serial scans included, that the multi-block passes spread over sixteen.
+constexpr int AR_G = AR_T / RS_T, AR_MAX_B = 2048, AR_MAX_VB = AR_MAX_B / RS_E;
+static_assert(AR_MAX_B % RS_E == 0 && AR_MAX_B <= 65536 && AR_MAX_B * 6 + 16384 <= 65536, "ids as 16-bit words, static LDS limit");
+
+__host__ __device__ inline size_t ar_val_bytes(long long B) { return ((size_t)B * 4 + 7) & ~(size_t)7; }
+
+__global__ void __launch_bounds__(AR_T) adaptive_resample_block_kernel(const float* __restrict__ logits, int B, double u0,
+                                                                       double theta, long long* __restrict__ ids,
+                                                                       long long* __restrict__ n_unique,
+                                                                       double* __restrict__ stats,
+                                                                       int* __restrict__ resampled) {
+  extern __shared__ double ar_lds[];
+  __shared__ StatsLds L;
+  __shared__ double part[AR_G][RS_T], red[AR_G][RS_T / 64], bsum[AR_MAX_VB], bw[AR_MAX_VB];
+  __shared__ float redf[AR_G][RS_T / 64], bmax[AR_MAX_VB];
+  float* val = reinterpret_cast<float*>(ar_lds);
+  unsigned short* par = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(ar_lds) + ar_val_bytes(B));
+  const int tid = threadIdx.x, g = tid / RS_T, t = tid % RS_T;
+  for (int i = tid; i < B; i += AR_T) val[i] = logits[i];
+  __syncthreads();
+  const int flag = logweight_stats_block(val, B, theta, stats, L);
+  if (tid == 0) *resampled = flag;
+  if (!flag) {  // uniform: every thread folded the same partials
+    for (int i = tid; i < B; i += AR_T) ids[i] = i;
+    if (tid == 0 && n_unique) *n_unique = B;
+    return;
+  }
+  const int nb = (B + RS_E - 1) / RS_E;
+  for (int v0 = 0; v0 < nb; v0 += AR_G) {  // A
+    const float m = rs_pass_max(val, B, v0 + g, t, redf[g]);
+    if (t == 0 && v0 + g < nb) bmax[v0 + g] = m;
+    __syncthreads();  // redf is read by t == 0 after the pass's own barrier
+  }
+  const float mx = rs_fold_max(bmax, nb);
+  for (int v0 = 0; v0 < nb; v0 += AR_G) {  // B
+    const double s = rs_pass_sum(val, B, v0 + g, t, mx, 1.0f, 0, red[g]);
+    if (t == 0 && v0 + g < nb) bsum[v0 + g] = s;
+  }
+  __syncthreads();
+  const float sm = (float)rs_fold_sum(bsum, nb);
+  for (int v0 = 0; v0 < nb; v0 += AR_G) {  // C
+    const double s = rs_pass_sum(val, B, v0 + g, t, mx, sm, 1, red[g]);
+    if (t == 0 && v0 + g < nb) bw[v0 + g] = s;
+  }
+  __syncthreads();
+  for (int v0 = 0; v0 < nb; v0 += AR_G) {  // D, in place
+    const int vb = v0 + g;
+    rs_pass_bins(val, B, vb, t, mx, sm, rs_fold_sum(bw, vb < nb ? vb : nb), part[g], val);
+  }
+  __syncthreads();
+  const float invB = (float)(1.0 / (double)B);
+  for (int k = tid; k < B; k += AR_T) {  // E
+    const long long id = rs_search(val, B, u0, invB, k);
+    ids[k] = id;
+    par[k] = (unsigned short)id;
+  }
+  __syncthreads();
+  long long runs = 0;
+  count_runs_block(par, B, &runs);  // thread 0 holds the count
+  if (tid == 0 && n_unique) *n_unique = runs;
+}
+
+// ---- the gated multi-pass event (B > AR_MAX_B): logweight_stats_kernel writes the flag, the passes of
+// pita_systematic_resample and the run count follow and test it on entry.  Flag clear: they return at once and the
+// search pass writes the identity; flag set: exactly the arithmetic of the plain kernels.
+__global__ void __launch_bounds__(RS_T) rs_max_gated_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                            long long B, float* __restrict__ bmax) {
+  if (*gate) rs_max_block(logits, B, bmax);
+}
+__global__ void __launch_bounds__(RS_T) rs_sum_gated_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                            long long B, int nblk, const float* __restrict__ bmax,
+                                                            const double* __restrict__ bsum, double* __restrict__ out,
+                                                            int phase) {
+  if (*gate) rs_sum_block(logits, B, nblk, bmax, bsum, out, phase);
+}
+__global__ void __launch_bounds__(RS_T) rs_bins_gated_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                             long long B, int nblk, const float* __restrict__ bmax,
+                                                             const double* __restrict__ bsum, const double* __restrict__ bw,
+                                                             float* __restrict__ bins) {
+  if (*gate) rs_bins_block(logits, B, nblk, bmax, bsum, bw, bins);
+}
+__global__ void __launch_bounds__(256) rs_search_gated_kernel(const int* __restrict__ gate, const float* __restrict__ bins,
+                                                              long long B, double u0, long long* __restrict__ ids) {
+  if (*gate) {
+    rs_search_grid(bins, B, u0, ids);
+  } else {
+    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < B; k += (long long)gridDim.x * 256) ids[k] = k;
+  }
+}
+__global__ void __launch_bounds__(1024) count_runs_gated_kernel(const int* __restrict__ gate, const long long* __restrict__ ids,
+                                                                long long B, long long* __restrict__ out) {
+  if (*gate) {
+    count_runs_block(ids, B, out);
+  } else if (threadIdx.x == 0) {
+    *out = B;
   }
 }
 
@@ -602,6 +832,65 @@ extern "C" int pita_systematic_resample(const float* logits, int64_t B, double u
   const long long sb = (B + 255) / 256;
   hipLaunchKernelGGL(rs_search_kernel, dim3((unsigned)(sb < 8192 ? sb : 8192)), dim3(256), 0, s, bins, (long long)B, u0,
                      (long long*)ids);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// one block of AR_T threads sweeps the vector: no scratch
+extern "C" size_t pita_logweight_stats_workspace_bytes(int64_t) { return 0; }
+
+extern "C" int pita_logweight_stats(const float* a, int64_t B, double* stats, void* /*workspace*/, void* stream) {
+  PITA_REQUIRE(a && stats && B >= 1, "pita_logweight_stats: bad argument (B >= 1, non-null a and stats)");
+  hipLaunchKernelGGL(logweight_stats_kernel, dim3(1), dim3(AR_T), 0, (hipStream_t)stream, a, (long long)B, 0.0, stats,
+                     (int*)nullptr);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+extern "C" int pita_adaptive_resample_single_launch(int64_t B) { return B >= 1 && B <= AR_MAX_B ? 1 : 0; }
+
+// the gated path's scratch is pita_systematic_resample's; the one-launch path needs none (8 bytes so that it is never null)
+extern "C" size_t pita_adaptive_resample_workspace_bytes(int64_t B) {
+  return pita_adaptive_resample_single_launch(B) ? 8 : pita_resample_workspace_bytes(B);
+}
+
+extern "C" int pita_adaptive_resample(const float* logits, int64_t B, double u0, double theta, int64_t* ids,
+                                      int64_t* n_unique, double* stats, int* resampled, void* workspace, void* stream) {
+  PITA_REQUIRE(B >= 1, "pita_adaptive_resample: B must be at least 1 (got %lld)", (long long)B);
+  PITA_REQUIRE(logits && ids && stats && resampled && workspace, "pita_adaptive_resample: null argument");
+  PITA_REQUIRE(theta >= 0.0 && theta <= 1.0, "pita_adaptive_resample: theta must be in [0, 1] (got %g)", theta);
+  PITA_REQUIRE(u0 >= 0.0 && u0 < 1.0, "pita_adaptive_resample: u0 must be in [0, 1) (got %g)", u0);
+  PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_adaptive_resample: workspace must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (pita_adaptive_resample_single_launch(B)) {
+    hipLaunchKernelGGL(adaptive_resample_block_kernel, dim3(1), dim3(AR_T), ar_val_bytes(B) + 2 * (size_t)B, s, logits,
+                       (int)B, u0, theta, (long long*)ids, (long long*)n_unique, stats, resampled);
+    PITA_LAUNCH_CHECK();
+    return PITA_OK;
+  }
+  const long long nb = rs_nblk(B);
+  char* w = static_cast<char*>(workspace);
+  float* bins = reinterpret_cast<float*>(w);
+  w += ((size_t)B * 4 + 7) & ~(size_t)7;
+  float* bmax = reinterpret_cast<float*>(w);
+  w += ((size_t)nb * 4 + 7) & ~(size_t)7;
+  double* bsum = reinterpret_cast<double*>(w);
+  double* bw = bsum + nb;
+  const int* gate = resampled;
+  hipLaunchKernelGGL(logweight_stats_kernel, dim3(1), dim3(AR_T), 0, s, logits, (long long)B, theta, stats, resampled);
+  hipLaunchKernelGGL(rs_max_gated_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, gate, logits, (long long)B, bmax);
+  hipLaunchKernelGGL(rs_sum_gated_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, gate, logits, (long long)B, (int)nb, bmax,
+                     bsum, bsum, 0);
+  hipLaunchKernelGGL(rs_sum_gated_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, gate, logits, (long long)B, (int)nb, bmax,
+                     bsum, bw, 1);
+  hipLaunchKernelGGL(rs_bins_gated_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, gate, logits, (long long)B, (int)nb, bmax,
+                     bsum, bw, bins);
+  const long long sb = (B + 255) / 256;
+  hipLaunchKernelGGL(rs_search_gated_kernel, dim3((unsigned)(sb < 8192 ? sb : 8192)), dim3(256), 0, s, gate, bins,
+                     (long long)B, u0, (long long*)ids);
+  if (n_unique)
+    hipLaunchKernelGGL(count_runs_gated_kernel, dim3(1), dim3(1024), 0, s, gate, (const long long*)ids, (long long)B,
+                       (long long*)n_unique);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

@@ -54,6 +54,32 @@ def histogram(values: torch.Tensor, edges) -> torch.Tensor:
     return counts
 
 
+_LOGWEIGHT_STATS = ("max", "log_mean_weight", "ess", "ess_fraction", "n_bad", "n_neg_inf")
+
+
+def logweight_stats(logw: torch.Tensor):
+    """Diagnostics of importance log-weights (pita_logweight_stats; fp64 sums in a fixed order): for a 1-D device tensor
+    a dict of Python floats -- ``max`` over the finite entries, ``log_mean_weight`` = log((1/B) sum exp(logw)), the
+    effective sample size ``ess`` = (sum w)^2 / sum w^2 and ``ess_fraction`` = ess / B, ``n_bad`` the number of NaN or
+    +inf entries (left out of every sum) and ``n_neg_inf`` the number of -inf entries (weight 0).  For ``[N, B]`` one
+    float64 numpy array of length N per key, one row at a time; one host transfer in either case."""
+    from . import _lib
+
+    a = _lib.dev_tensor(logw, "logw")
+    if a.dim() not in (1, 2) or a.shape[-1] < 1:
+        raise ValueError(f"logweight_stats expects [B] or [N, B] log-weights with B >= 1, got {tuple(a.shape)}")
+    rows = a.reshape(-1, a.shape[-1])
+    out = torch.empty(rows.shape[0], 6, dtype=torch.float64, device=a.device)
+    L, st = _lib.lib(), _lib.stream_ptr(a.device)
+    for k in range(rows.shape[0]):
+        _lib.check(L.pita_logweight_stats(rows[k].data_ptr(), rows.shape[1], out[k].data_ptr(), None, st),
+                   "pita_logweight_stats")
+    h = out.cpu().numpy()
+    if a.dim() == 1:
+        return {name: float(h[0, j]) for j, name in enumerate(_LOGWEIGHT_STATS)}
+    return {name: h[:, j].copy() for j, name in enumerate(_LOGWEIGHT_STATS)}
+
+
 def _density(counts: torch.Tensor, edges):
     import numpy as np
 

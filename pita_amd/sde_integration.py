@@ -28,8 +28,9 @@ import torch
 
 from . import _lib
 from .data_utils import remove_mean
+from .metrics import logweight_stats
 from .sdes import SDETerms, TermStats, VEReverseSDE  # noqa: F401
-from .utils import gather_rows, sample_cat_sys
+from .utils import gather_rows, sample_cat_sys, sample_cat_sys_adaptive
 
 
 def _scalar(v):
@@ -221,6 +222,28 @@ def _host_counts(counts):
     return counts
 
 
+class _EventLog:
+    """Per-step outputs of the adaptive resampling events of one run (``ess_threshold``), preallocated on the device:
+    the kernel of step s writes row s, the host reads everything once after the loop (``finish``)."""
+
+    def __init__(self, N, B, device):
+        self.stats = torch.full((N, 6), float("nan"), dtype=torch.float64, device=device)
+        self.flags = torch.zeros(N, dtype=torch.int32, device=device)
+        self.counts = torch.full((N,), B, dtype=torch.int64, device=device)
+
+    def row(self, step):
+        return self.flags[step], self.stats[step], self.counts[step]
+
+    def finish(self, final_logweights):
+        """``last_weight_stats``; ``final_logweights``: the last row of the run's log-weights (device)."""
+        h = self.stats.cpu().numpy()
+        resampled = self.flags.cpu().numpy() != 0
+        lmw = h[:, 1].copy()
+        tail = logweight_stats(final_logweights)["log_mean_weight"]
+        return {"ess": h[:, 2].copy(), "ess_fraction": h[:, 3].copy(), "log_mean_weight": lmw, "resampled": resampled,
+                "log_z": float(lmw[resampled].sum()) + tail}
+
+
 def _terms_from_stats(st4, st8, n_elem, n_walk, computed, debiased):
     """N light SDETerms from the per-step moment buffers (host copies happen once, here).  st4: [N, 4] drift_X /
     diffusion moments; st8: [N, 8] drift_A, divergence_score, cross_term, dUt_dt moments (debiased regime only)."""
@@ -245,7 +268,21 @@ class WeightedSDEIntegrator:
                  partial_annealing_factor_schedule=None, reverse_time=True, diffusion_scale=1.0, time_range=1.0,
                  resampling_interval=-1, num_negative_time_steps=100, post_mcmc_steps=100, adaptive_mcmc=False,
                  batch_size=None, no_grad=True, resample_at_end=False, dt_negative_time=1e-4, do_langevin=False,
-                 should_mean_free=True, seed=0, record_terms=False, verbose=False):
+                 should_mean_free=True, seed=0, record_terms=False, verbose=False, ess_threshold=None):
+        """``ess_threshold``: None (the reference's fixed schedule: every due event resamples) or a fraction in [0, 1] --
+        a due event then resamples only when the effective sample size of the log-weights is at most
+        ``ess_threshold * batch``, decided on the device (``sample_cat_sys_adaptive``; an extension the reference does
+        not have), and ``last_weight_stats`` holds the per-event diagnostics of the last run."""
+        if ess_threshold is not None:
+            try:
+                ok = 0.0 <= float(ess_threshold) <= 1.0  # NaN fails both comparisons
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"ess_threshold must be None or a fraction in [0, 1], got {ess_threshold!r}")
+            ess_threshold = float(ess_threshold)
+        self.ess_threshold = ess_threshold
+        self.last_weight_stats = None
         self.sde = sde
         self.num_integration_steps = num_integration_steps
         self.start_resampling_step, self.end_resampling_step = start_resampling_step, end_resampling_step
@@ -351,6 +388,13 @@ class WeightedSDEIntegrator:
                                             energy_function, annealing_factor_schedule, inverse_temperature,
                                             resampling_interval, u_iter, mala_draws)
 
+        due = events
+        if self.ess_threshold is not None and self.ess_threshold < 1.0:
+            # the weights are identically zero here, so ESS = B at every due event: none of them resamples (decided on the
+            # host, no kernel); their uniforms are still drawn, as the fixed schedule would draw them
+            for _ in events:
+                comm.shared_uniform(next(u_iter) if u_iter is not None else None)
+            events = []
         s = start
         bounds = events + [N - 1]
         for stop in bounds:  # run steps s..stop inclusive, then (maybe) resample
@@ -379,6 +423,13 @@ class WeightedSDEIntegrator:
                                                         inverse_temperature, u_iter, off, Bl)
             logweights = torch.cat([logweights, a_next[None]])
             num_unique_idxs.append(n_unique)
+        if self.ess_threshold is not None:  # zero log-weights at every due event: ESS = B, mean weight 1
+            at = np.zeros(N, dtype=bool)
+            at[due] = True
+            self.last_weight_stats = {
+                "ess": np.where(at, float(comm.world * Bl), np.nan), "ess_fraction": np.where(at, 1.0, np.nan),
+                "log_mean_weight": np.where(at, 0.0, np.nan), "resampled": at & (self.ess_threshold >= 1.0),
+                "log_z": logweight_stats(logweights[-1])["log_mean_weight"]}
 
         if self.num_negative_time_steps > 0:
             x = self.negative_time_descent(x, energy_function, walker_offset=off)
@@ -402,6 +453,7 @@ class WeightedSDEIntegrator:
         dev = x.device
         L = _lib.lib()
         zero_a = torch.zeros(Bl, device=dev)  # never written to: every update of `a` makes a new tensor
+        adaptive = _EventLog(N, comm.world * Bl, dev) if self.ess_threshold is not None else None
         a = zero_a
         logweights, num_unique_idxs, sde_terms_all = [], [], []
         bs = self.batch_size or Bl
@@ -445,7 +497,16 @@ class WeightedSDEIntegrator:
             n_unique = Bg
             due = not (resampling_interval == -1 or (step + 1) % resampling_interval != 0
                        or step >= self.end_resampling_step)
-            if due:
+            if due and adaptive is not None:
+                # the event is decided on the device: no host read here, every rank decides alike on the gathered vector;
+                # the uniform is drawn whether or not the event resamples (the fixed schedule's stream)
+                ag = comm.all_gather(a)
+                u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
+                ids, resampled, _, n_unique = sample_cat_sys_adaptive(ag.shape[0], ag, self.ess_threshold, u,
+                                                                      out=adaptive.row(step))
+                x = comm.exchange_rows(x, ids, Bl)  # identity ids move nothing
+                a = torch.where(resampled != 0, zero_a, a)
+            elif due:
                 ag = comm.all_gather(a)
                 u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
                 ids, _ = sample_cat_sys(ag.shape[0], ag, u)
@@ -469,6 +530,8 @@ class WeightedSDEIntegrator:
                                                         off, Bl)
             logweights = torch.cat([logweights, a_next[None]])
             num_unique_idxs.append(n_unique)
+        if adaptive is not None:
+            self.last_weight_stats = adaptive.finish(logweights[-1])
         if self.num_negative_time_steps > 0:
             x = self.negative_time_descent(x, energy_function, walker_offset=off)
         acceptance_rate_list = []
