@@ -14,13 +14,13 @@ import ctypes
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib
-from .egnn_temp_conditioned import EGNN, _as_batch
+from ._backbone import HipBackbone
+from .egnn_temp_conditioned import EGNN
 
 
-class EGNN_dynamics_AD2_cat(nn.Module):
+class EGNN_dynamics_AD2_cat(HipBackbone):
     def __init__(self, n_particles, n_dimensions, hidden_nf=64, act_fn=torch.nn.SiLU(), n_layers=5, recurrent=True,
                  attention=True, tanh=True, atom_encoding_filename="atom_types_ecoding.npy", data_dir="data/alanine",
                  pdb_filename="", agg="sum", M=128, condition_beta=False, h_initial=None):
@@ -35,8 +35,6 @@ class EGNN_dynamics_AD2_cat(nn.Module):
                          recurrent=recurrent, attention=attention, tanh=tanh, agg=agg)
         self.counter = 0
         self.M = M
-        self._handle = None
-        self._handle_key = None
 
     def get_h_initial(self):
         """The static node features of :66-92 for the particle counts that need no topology file."""
@@ -55,30 +53,24 @@ class EGNN_dynamics_AD2_cat(nn.Module):
             f"EGNN_dynamics_AD2_cat: the node features of {n} particles come from a topology file (mdtraj, :94-155); "
             "pass h_initial=[n_particles, n_features] instead")
 
-    # ------------------------------------------------------------------ native handle
+    # ------------------------------------------------------------------ native handle (lifetime: HipBackbone)
+    _destroy_symbol = "pita_egnn_wide_destroy"
+
     def _config(self):
         e = self.egnn
         return _lib.EgnnWideConfig(self._n_particles, self._n_dimensions, e.hidden_nf, e.n_layers,
                                    int(self.h_initial.size(1)), int(bool(self.condition_beta)), int(e.attention),
                                    int(e.tanh), e.coords_range)
 
-    def _native(self, device):
-        tensors = self.__dict__.get("_tensor_list")
-        if tensors is None:
-            tensors = self.__dict__["_tensor_list"] = list(self.parameters()) + list(self.buffers())
-        key = (device.index,) + tuple((p.data_ptr(), p._version) for p in tensors)
-        if self._handle is None or key != self._handle_key:
-            self._release()
-            flat = torch.cat([p.detach().to("cpu", torch.float32).reshape(-1) for p in self.state_dict().values()]).contiguous().numpy()
-            h0 = np.ascontiguousarray(self.h_initial.detach().to("cpu", torch.float32).numpy())
-            cfg = self._config()
-            h = ctypes.c_void_p()
-            with torch.cuda.device(device):
-                _lib.check(_lib.lib().pita_egnn_wide_create(ctypes.byref(h), ctypes.byref(cfg),
-                                                            flat.ctypes.data_as(ctypes.c_void_p), flat.size,
-                                                            h0.ctypes.data_as(ctypes.c_void_p)), "pita_egnn_wide_create")
-            self._handle, self._handle_key = h, key
-        return self._handle
+    def _create_handle(self, flat):
+        h0 = np.ascontiguousarray(self.h_initial.detach().to("cpu", torch.float32).numpy())
+        cfg, h = self._config(), ctypes.c_void_p()
+        _lib.check(_lib.lib().pita_egnn_wide_create(ctypes.byref(h), ctypes.byref(cfg), flat.ctypes.data_as(ctypes.c_void_p),
+                                                    flat.size, h0.ctypes.data_as(ctypes.c_void_p)), "pita_egnn_wide_create")
+        return h
+
+    def _conditions_on_beta(self):
+        return self.condition_beta
 
     def uses_matrix_pipe(self, device):
         """True when evaluations on ``device`` run on the MFMA kernel (the instantiated particle counts, unless
@@ -95,46 +87,15 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         PITA_WIDE_NO_MFMA is set); the vector-pipe kernel alone computes it otherwise."""
         return bool(_lib.lib().pita_egnn_wide_vjp_uses_matrix_pipe(self._native(torch.device(device))))
 
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_handle"], state["_handle_key"] = None, None
-        state.pop("_tensor_list", None)
-        return state
-
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().pita_egnn_wide_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
     # ------------------------------------------------------------------ reference interface
-    def _eval(self, what, t, xs, beta):
-        xs = _lib.dev_tensor(xs, "xs")
-        B = xs.shape[0]
-        t = _lib.dev_tensor(t, "t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_beta:
-            if beta is None:
-                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
-            b = _as_batch(beta, B, xs.device)
-        out = torch.empty_like(xs)
-        _lib.check(_lib.lib().pita_egnn_wide_eval(self._native(xs.device), int(what), t.data_ptr(), xs.data_ptr(), _lib.ptr(b),
-                                                  out.data_ptr(), B, _lib.stream_ptr(xs.device)), "pita_egnn_wide_eval")
-        return out
-
     def forward(self, t, xs, beta=None):
         """vel[B, n*d] = backbone(t[B], xs[B, n*d], beta[B]); mean-free (:157-203)."""
         self.counter += 1
-        return self._eval(0, t, xs, beta)
+        return self._edm_call("pita_egnn_wide_eval", 0, t, xs, beta)
 
     def edm(self, what, h_t, x_t, beta):
         """what=1: denoiser D_theta, what=2: score (D_theta - x)/h, EDM preconditioning fused (score_net.py:13-43)."""
-        return self._eval(what, h_t, x_t, beta)
+        return self._edm_call("pita_egnn_wide_eval", what, h_t, x_t, beta)
 
     def can_fuse(self, n_particles, n_dim):
         return int(n_particles) == self._n_particles and int(n_dim) == self._n_dimensions
@@ -164,49 +125,15 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         kernel where ``jvp_uses_matrix_pipe``, the fp32 vector-pipe kernel otherwise).  With it ``VEReverseSDE(debias_inference=True)`` runs on this backbone: the exact divergence of the
         score (utils.py:30-51), grad_x E_theta (energy_net.py:51-62) and dE_theta/dt (sdes.py:218) are assembled from
         dim + 1 such launches per net (sdes.py's forward-mode path)."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_beta:
-            if beta is None:
-                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
-            b = _as_batch(beta, B, x_t.device)
-        if vx is not None:
-            vx = _lib.dev_tensor(vx, "vx")
-        if vh is not None:
-            vh = _lib.dev_tensor(vh, "vh").reshape(-1).expand(B).contiguous()
-        out = torch.empty_like(x_t) if want_primal else None
-        dout = torch.empty_like(x_t) if want_tangent else None
-        stride = 1
-        if dot_out is not None:
-            assert dot_out.is_cuda and dot_out.dtype == torch.float32 and dot_out.is_contiguous()
-            stride = dot_out.shape[1] if dot_out.dim() == 2 else 1
-        _lib.check(_lib.lib().pita_egnn_wide_jvp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                                 _lib.ptr(vx), int(direction), _lib.ptr(vh), _lib.ptr(out), _lib.ptr(dout),
-                                                 _lib.ptr(dot_out), stride, int(dot_col), _lib.ptr(diag_acc), B,
-                                                 _lib.stream_ptr(x_t.device)), "pita_egnn_wide_jvp")
-        return out, dout
+        return self._jvp_call("pita_egnn_wide_jvp", h_t, x_t, beta, vx, direction, vh, want_primal, want_tangent, dot_out,
+                              dot_col, diag_acc)
 
     def jacobian_trace(self, h_t, x_t, beta, want_denoiser=False):
         """(trace, D or None): trace(J_x D_theta(h, x)) per walker, exactly, over all n*d unit directions, and with
         ``want_denoiser`` D_theta(h, x) -- ONE call (pita_egnn_wide_jacobian_trace: one launch over (walker, direction)
         pairs and a reduction) with the bits of the n*d ``jvp(direction=k, diag_acc=trace)`` launches it replaces.
         ``VEReverseSDE._score_divergence_terms`` takes it for the exact divergence of the score (utils.py:30-51)."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_beta:
-            if beta is None:
-                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
-            b = _as_batch(beta, B, x_t.device)
-        trace = torch.empty(B, device=x_t.device)
-        den = torch.empty_like(x_t) if want_denoiser else None
-        _lib.check(_lib.lib().pita_egnn_wide_jacobian_trace(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(),
-                                                            _lib.ptr(b), trace.data_ptr(), _lib.ptr(den), B,
-                                                            _lib.stream_ptr(x_t.device)), "pita_egnn_wide_jacobian_trace")
-        return trace, den
+        return self._trace_call("pita_egnn_wide_jacobian_trace", h_t, x_t, beta, want_denoiser)
 
     def jacobian_trace_estimate(self, h_t, x_t, beta, n_probes, probes=None, seed=0, walker_offset=0, step=0,
                                 want_denoiser=False, want_per_probe=False):
@@ -217,27 +144,8 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         (parity hook); None: Rademacher signs drawn in the kernel, keyed (seed, walker_offset + row, step) like the
         samplers' noise -- what ``pita_amd.utils.rademacher_probes`` returns for the same key (K <= 256).
         ``want_per_probe``: also the [K, B] quadratic forms.  ``VEReverseSDE(divergence="hutchinson")`` takes it."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        K = int(n_probes)
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_beta:
-            if beta is None:
-                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
-            b = _as_batch(beta, B, x_t.device)
-        if probes is not None:
-            probes = _lib.dev_tensor(probes, "probes")
-            if tuple(probes.shape) != (K, B, x_t.shape[1]):
-                raise ValueError(f"probes has shape {tuple(probes.shape)}, expected {(K, B, x_t.shape[1])}")
-        est = torch.empty(B, device=x_t.device)
-        den = torch.empty_like(x_t) if want_denoiser else None
-        per = torch.empty(max(K, 0), B, device=x_t.device) if want_per_probe else None
-        _lib.check(_lib.lib().pita_egnn_wide_trace_probes(
-            self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b), K, _lib.ptr(probes),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step), est.data_ptr(), _lib.ptr(per), _lib.ptr(den), B,
-            _lib.stream_ptr(x_t.device)), "pita_egnn_wide_trace_probes")
-        return est, den, per
+        return self._probes_call("pita_egnn_wide_trace_probes", h_t, x_t, beta, n_probes, probes, seed, walker_offset, step,
+                                 want_denoiser, want_per_probe)
 
     vjp_h_parts = True  # vjp(..., want_h_parts=True) is available
 
@@ -248,26 +156,4 @@ class EGNN_dynamics_AD2_cat(nn.Module):
         ``want_h_parts`` (with want_dot_h): also [B, 2] = (c_out <cot, F>, <cot, d(c_out F)/dh>), the split of the same
         derivative that pita_fk_assemble turns into E_theta and dE_theta/dh without cancellation at small h
         -> (D, vjp, dot_h, parts)."""
-        if want_h_parts and not want_dot_h:
-            raise ValueError("want_h_parts needs want_dot_h")
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_beta:
-            if beta is None:
-                raise ValueError("EGNN_dynamics_AD2_cat(condition_beta=True) needs beta")
-            b = _as_batch(beta, B, x_t.device)
-        if cot is not None:
-            cot = _lib.dev_tensor(cot, "cot")
-        out = torch.empty_like(x_t) if want_primal else None
-        vjp = torch.empty_like(x_t)
-        dot_h = torch.empty(B, device=x_t.device) if want_dot_h else None
-        parts = torch.empty(B, 2, device=x_t.device) if want_h_parts else None
-        _lib.check(_lib.lib().pita_egnn_wide_vjp_parts(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                                       _lib.ptr(cot), _lib.ptr(out), vjp.data_ptr(), _lib.ptr(dot_h),
-                                                       _lib.ptr(parts), B, _lib.stream_ptr(x_t.device)),
-                   "pita_egnn_wide_vjp_parts")
-        if want_h_parts:
-            return out, vjp, dot_h, parts
-        return (out, vjp, dot_h) if want_dot_h else (out, vjp)
+        return self._vjp_call("pita_egnn_wide_vjp_parts", h_t, x_t, beta, cot, want_primal, want_dot_h, want_h_parts)

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._backbone import HipBackbone
 
 
 DEFAULT_PRECISION = "f16x2"  # dense-layer arithmetic of the HIP EGNN when the caller does not choose (see EGNN_dynamics)
@@ -58,7 +59,7 @@ class EGNN(nn.Module):
             self.add_module("gcl_%d" % i, _GCLParams(hidden_nf, act_fn, attention, tanh, in_edge_nf))
 
 
-class EGNN_dynamics(nn.Module):
+class EGNN_dynamics(HipBackbone):
     def __init__(self, n_particles, n_dimension, hidden_nf=64, act_fn=torch.nn.SiLU(), n_layers=4, recurrent=True,
                  attention=False, condition_time=True, tanh=False, agg="sum", energy=False, add_virtual=False,
                  condition_temperature=False, feature_layout="pita", precision=None):
@@ -78,83 +79,39 @@ class EGNN_dynamics(nn.Module):
         precision = precision or os.environ.get("PITA_EGNN_PRECISION", DEFAULT_PRECISION)
         self.precision = {"f32": 0, "bf16x3": 1, "f16x2": 2}[precision]
         self.counter = 0
-        self._handle = None
-        self._handle_key = None
 
-    # ------------------------------------------------------------------ native handle
+    # ------------------------------------------------------------------ native handle (lifetime: HipBackbone)
+    _destroy_symbol = "pita_egnn_destroy"
+
     def _config(self):
         e = self.egnn
         return _lib.EgnnConfig(self._n_particles, self._n_dimension, e.hidden_nf, e.n_layers, self.in_node_nf,
                                int(e.attention), int(e.tanh), e.coords_range, self.feature_layout, self.precision)
 
-    def _native(self, device):
-        # cheap staleness check on every call: (storage pointer, version counter) of every parameter/buffer
-        tensors = self.__dict__.get("_tensor_list")
-        if tensors is None:
-            tensors = self.__dict__["_tensor_list"] = list(self.parameters()) + list(self.buffers())
-        key = (device.index, self.precision) + tuple((p.data_ptr(), p._version) for p in tensors)
-        if self._handle is None or key != self._handle_key:
-            self._release()
-            params = list(self.state_dict().values())
-            flat = torch.cat([p.detach().to("cpu", torch.float32).reshape(-1) for p in params]).contiguous().numpy()
-            cfg = self._config()
-            h = ctypes.c_void_p()
-            with torch.cuda.device(device):
-                _lib.check(_lib.lib().pita_egnn_create(ctypes.byref(h), ctypes.byref(cfg),
-                                                       flat.ctypes.data_as(ctypes.c_void_p), flat.size),
-                           "pita_egnn_create")
-            self._handle, self._handle_key = h, key
-        return self._handle
+    def _create_handle(self, flat):
+        cfg, h = self._config(), ctypes.c_void_p()
+        _lib.check(_lib.lib().pita_egnn_create(ctypes.byref(h), ctypes.byref(cfg), flat.ctypes.data_as(ctypes.c_void_p),
+                                               flat.size), "pita_egnn_create")
+        return h
 
-    def __getstate__(self):
-        """The native handle is a per-process device resource: copies / pickles start without one."""
-        state = self.__dict__.copy()
-        state["_handle"], state["_handle_key"] = None, None
-        state.pop("_tensor_list", None)
-        return state
+    def _key_extra(self):
+        return (self.precision,)
 
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().pita_egnn_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    def _conditions_on_beta(self):
+        return self.condition_temperature
 
     # ------------------------------------------------------------------ reference interface
     def forward(self, t, xs, beta=None):
         """vel[B, n*d] = backbone(t[B], xs[B, n*d], beta[B]); mean-free (:56-93)."""
-        xs = _lib.dev_tensor(xs, "xs")
-        B = xs.shape[0]
-        t = _lib.dev_tensor(t, "t").reshape(-1).expand(B).contiguous()
-        if self.condition_temperature:
-            if beta is None:
-                raise ValueError("EGNN_dynamics(condition_temperature=True).forward needs beta")
-            beta = _lib.dev_tensor(beta, "beta").reshape(-1).expand(B).contiguous()
-        else:
-            beta = None
-        out = torch.empty_like(xs)
-        _lib.check(_lib.lib().pita_egnn_forward(self._native(xs.device), t.data_ptr(), xs.data_ptr(), _lib.ptr(beta),
-                                                out.data_ptr(), B, _lib.stream_ptr(xs.device)), "pita_egnn_forward")
+        out = self._forward_call("pita_egnn_forward", t, xs, beta)
         self.counter += 1
         return out
 
     # ------------------------------------------------------------------ fused extensions used by ScoreNet / the sampler
+    # (who probes for which of them: the table in _backbone.py)
     def edm(self, what, h_t, x_t, beta):
         """what=1: denoiser D_theta, what=2: score (D_theta - x)/h, EDM preconditioning fused (score_net.py:13-43)."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_temperature:
-            b = _as_batch(beta, B, x_t.device)
-        out = torch.empty_like(x_t)
-        _lib.check(_lib.lib().pita_egnn_edm(self._native(x_t.device), what, h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                            out.data_ptr(), B, _lib.stream_ptr(x_t.device)), "pita_egnn_edm")
-        return out
+        return self._edm_call("pita_egnn_edm", what, h_t, x_t, beta)
 
     def jvp(self, h_t, x_t, beta, vx=None, direction=-1, vh=None, want_primal=True, want_tangent=True, dot_out=None,
             dot_col=0, diag_acc=None):
@@ -163,42 +120,14 @@ class EGNN_dynamics(nn.Module):
         every walker (-1 = zero).  ``vh``: [B] tensor or None.  Optional in-kernel reductions:
         ``dot_out[:, dot_col] = <x, dD>`` and ``diag_acc += dD[:, direction]``.
         (pita_egnn_jvp; fp32-accurate bf16x3 arithmetic.)"""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = _as_batch(beta, B, x_t.device) if self.condition_temperature else None
-        if vx is not None:
-            vx = _lib.dev_tensor(vx, "vx")
-        if vh is not None:
-            vh = _lib.dev_tensor(vh, "vh").reshape(-1).expand(B).contiguous()
-        out = torch.empty_like(x_t) if want_primal else None
-        dout = torch.empty_like(x_t) if want_tangent else None
-        stride = 1
-        if dot_out is not None:
-            assert dot_out.is_cuda and dot_out.dtype == torch.float32 and dot_out.is_contiguous()
-            stride = dot_out.shape[1] if dot_out.dim() == 2 else 1
-        _lib.check(_lib.lib().pita_egnn_jvp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                            _lib.ptr(vx), int(direction), _lib.ptr(vh), _lib.ptr(out), _lib.ptr(dout),
-                                            _lib.ptr(dot_out), stride, int(dot_col), _lib.ptr(diag_acc), B,
-                                            _lib.stream_ptr(x_t.device)), "pita_egnn_jvp")
-        return out, dout
+        return self._jvp_call("pita_egnn_jvp", h_t, x_t, beta, vx, direction, vh, want_primal, want_tangent, dot_out,
+                              dot_col, diag_acc)
 
     def jacobian_trace(self, h_t, x_t, beta, want_denoiser=False):
         """trace(J_x D_theta(h, x)) per walker, exactly, over all dim unit directions (pita_egnn_jacobian_trace: the
         primal network is evaluated once, its per-edge factors cached for the tangent-only launches that follow).
         ``want_denoiser``: also return D_theta(h, x), a by-product of the primal -> (trace, D)."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B, D = x_t.shape
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = _as_batch(beta, B, x_t.device) if self.condition_temperature else None
-        L = _lib.lib()
-        net = self._native(x_t.device)
-        trace = torch.empty(B, device=x_t.device)
-        den = torch.empty_like(x_t) if want_denoiser else None
-        with torch.cuda.device(x_t.device):
-            _lib.check(L.pita_egnn_jacobian_trace(net, h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b), trace.data_ptr(),
-                                                  _lib.ptr(den), B, _lib.stream_ptr(x_t.device)),
-                       "pita_egnn_jacobian_trace")
+        trace, den = self._trace_call("pita_egnn_jacobian_trace", h_t, x_t, beta, want_denoiser, device_guard=True)
         return (trace, den) if want_denoiser else trace
 
     def trace_probes(self, h_t, x_t, beta, n_probes, probes=None, seed=0, walker_offset=0, step=0, want_denoiser=False,
@@ -212,37 +141,13 @@ class EGNN_dynamics(nn.Module):
         quadratic forms.  Returns None when the particle system has no multi-direction kernel (PITA_EUNSUPPORTED): the
         caller takes ``n_probes`` ``jvp`` launches.  ``VEReverseSDE(divergence="hutchinson", shared_primal=True)``
         takes it."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        K = int(n_probes)
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = None
-        if self.condition_temperature:
-            if beta is None:
-                raise ValueError("EGNN_dynamics(condition_temperature=True) needs beta")
-            b = _as_batch(beta, B, x_t.device)
-        if probes is not None:
-            probes = _lib.dev_tensor(probes, "probes")
-            if tuple(probes.shape) != (K, B, x_t.shape[1]):
-                raise ValueError(f"probes has shape {tuple(probes.shape)}, expected {(K, B, x_t.shape[1])}")
-        est = torch.empty(B, device=x_t.device)
-        den = torch.empty_like(x_t) if want_denoiser else None
-        per = torch.empty(max(K, 0), B, device=x_t.device) if want_per_probe else None
         try:
-            net = self._native(x_t.device)
+            return self._probes_call("pita_egnn_trace_probes", h_t, x_t, beta, n_probes, probes, seed, walker_offset, step,
+                                     want_denoiser, want_per_probe, device_guard=True)
         except _lib.PitaHipError as e:
-            if getattr(e, "code", 0) == -2:  # PITA_EUNSUPPORTED: the library has no kernel at all for this system
+            if getattr(e, "code", 0) == -2:  # PITA_EUNSUPPORTED, from creating the handle or from the call
                 return None
             raise
-        with torch.cuda.device(x_t.device):
-            rc = _lib.lib().pita_egnn_trace_probes(
-                net, h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b), K, _lib.ptr(probes),
-                int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step), est.data_ptr(), _lib.ptr(per), _lib.ptr(den),
-                B, _lib.stream_ptr(x_t.device))
-        if rc == -2:  # PITA_EUNSUPPORTED
-            return None
-        _lib.check(rc, "pita_egnn_trace_probes")
-        return est, den, per
 
     vjp_h_parts = True  # vjp(..., want_h_parts=True) is available
 
@@ -253,24 +158,7 @@ class EGNN_dynamics(nn.Module):
         ``want_h_parts`` (with want_dot_h): also [B, 2] = (c_out <cot, F>, <cot, d(c_out F)/dh>), the split of the same
         derivative that pita_fk_assemble turns into E_theta and dE_theta/dh without cancellation at small h
         -> (D, vjp, dot_h, parts)."""
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = _as_batch(beta, B, x_t.device) if self.condition_temperature else None
-        if cot is not None:
-            cot = _lib.dev_tensor(cot, "cot")
-        out = torch.empty_like(x_t) if want_primal else None
-        vjp = torch.empty_like(x_t)
-        dot_h = torch.empty(B, device=x_t.device) if want_dot_h else None
-        if want_h_parts and not want_dot_h:
-            raise ValueError("want_h_parts needs want_dot_h")
-        parts = torch.empty(B, 2, device=x_t.device) if want_h_parts else None
-        _lib.check(_lib.lib().pita_egnn_vjp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                            _lib.ptr(cot), _lib.ptr(out), vjp.data_ptr(), _lib.ptr(dot_h),
-                                            _lib.ptr(parts), B, _lib.stream_ptr(x_t.device)), "pita_egnn_vjp")
-        if want_h_parts:
-            return out, vjp, dot_h, parts
-        return (out, vjp, dot_h) if want_dot_h else (out, vjp)
+        return self._vjp_call("pita_egnn_vjp", h_t, x_t, beta, cot, want_primal, want_dot_h, want_h_parts)
 
     def sampler_run(self, x, step_tab, n_steps, noise=None, seed=0, walker_offset=0, step0=0, remove_mean=True,
                     drift_out=None, n_particles=None, n_dim=None, stats_out=None):
@@ -287,7 +175,6 @@ class EGNN_dynamics(nn.Module):
             _lib.ptr(drift_out), _lib.ptr(stats_out), _lib.stream_ptr(x.device)), "pita_egnn_sampler_run")
         return x
 
-
     def sampler_work(self, B, device):
         """(16-bit MFMAs, f32 MFMAs) executed per walker-step by the fused sampler at batch B (pita_egnn_sampler_work)."""
         a, b = ctypes.c_double(), ctypes.c_double()
@@ -303,8 +190,3 @@ class EGNN_dynamics(nn.Module):
                                                         ctypes.byref(s)), "pita_egnn_sampler_mapping")
         return g.value, w.value, s.value
 
-
-def _as_batch(v, B, device):
-    if isinstance(v, torch.Tensor):
-        return _lib.dev_tensor(v.to(device), "beta").reshape(-1).expand(B).contiguous()
-    return torch.full((B,), float(v), device=device, dtype=torch.float32)

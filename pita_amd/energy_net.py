@@ -3,16 +3,14 @@
 * ``forward_energy`` -- E_theta(h, x) (energy_net.py:14-49): one backbone forward on the EDM-scaled input
   (``pita_edm_scale_input``), then the per-walker reduction kernel ``pita_energy_theta``.
 * ``forward`` -- grad_x E_theta (autograd in the reference, :51-62): grad E = ((1 + c_s) x - D - J_x D^T x) / h with
-  J_x D^T x from the backbone's ``vjp`` -- ONE reverse-mode launch of the HIP EGNN (``EGNN_dynamics.vjp``), ONE
-  forward-mode launch over all D unit tangents of the HIP MLP (``MyMLP.vjp`` / ``MyMLPTemperature.vjp``,
-  pita_mlp_jacobian); backbones with a single-direction forward-mode derivative only (``EGNN_dynamics_AD2_cat.jvp``)
-  assemble it from one launch per direction.
+  J_x D^T x from the backbone's ``vjp`` (one launch), or, from a backbone with ``jvp`` only, one launch per direction.
+  What the two must return and which backbones offer them: the protocol table in ``_backbone.py``.
 """
 import torch
 from torch import nn
 
 from . import _lib
-from .score_net import _Preconditioned
+from ._backbone import as_batch
 
 
 class EnergyNet(nn.Module):
@@ -21,7 +19,7 @@ class EnergyNet(nn.Module):
         self.net = score_net  # registered as ``net`` (not ``model``): state_dict keys match the reference's
         self.precondition_beta = precondition_beta
 
-    _batch = staticmethod(_Preconditioned._batch)
+    _batch = staticmethod(as_batch)
 
     def reinitialize(self, score_net: nn.Module):
         self.net = score_net
@@ -56,7 +54,7 @@ class EnergyNet(nn.Module):
         h = self._batch(ht, x.shape[0], x.device)
         if hasattr(self.net, "vjp"):
             Dx, jtx = self.net.vjp(h, x, beta)
-        else:  # forward-mode backbone (EGNN_dynamics_AD2_cat): (J^T x)_k = <x, J e_k>, one launch per direction
+        else:  # forward-mode backbone: (J^T x)_k = <x, J e_k>, one launch per direction
             jtx, Dx = torch.empty_like(x), None
             for k in range(x.shape[1]):
                 out, _ = self.net.jvp(h, x, beta, direction=k, want_primal=(k == 0), want_tangent=False, dot_out=jtx,

@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._backbone import HipBackbone
 
 
 class _Block(nn.Module):  # parameter holder for mlp.py:100-118 (x + GELU(ff(x)))
@@ -21,8 +22,9 @@ class _Block(nn.Module):  # parameter holder for mlp.py:100-118 (x + GELU(ff(x))
         self.ff = nn.Linear(size, size)
 
 
-class _HipMLP(nn.Module):
+class _HipMLP(HipBackbone):
     _temperature = False
+    _destroy_symbol = "pita_mlp_destroy"
 
     def __init__(self, hidden_size=128, hidden_layers=3, emb_size=128, out_dim=2, time_emb="sinusoidal",
                  input_emb="sinusoidal", add_t_emb=False, concat_t_emb=False, input_dim=2, energy_function=None):
@@ -36,101 +38,41 @@ class _HipMLP(nn.Module):
         layers += [_Block(hidden_size) for _ in range(hidden_layers)]
         layers.append(nn.Linear(emb_size, out_dim))  # sized by emb_size like the reference (mlp.py:238-239)
         self.joint_mlp = nn.Sequential(*layers)
-        self._handle, self._handle_key = None, None
 
     def _freqs(self):
         half = self.emb_size // 2  # the reference's fp32 torch ops (mlp.py:19-21)
         w = torch.log(torch.Tensor([10000.0])) / (half - 1)
         return torch.exp(-w * torch.arange(half)).contiguous()
 
-    def _native(self, device):
-        tensors = self.__dict__.get("_tensor_list")
-        if tensors is None:
-            tensors = self.__dict__["_tensor_list"] = list(self.parameters()) + list(self.buffers())
-        key = (device.index,) + tuple((p.data_ptr(), p._version) for p in tensors)
-        if self._handle is None or key != self._handle_key:
-            self._release()
-            params = list(self.state_dict().values())
-            flat = torch.cat([p.detach().to("cpu", torch.float32).reshape(-1) for p in params]).contiguous().numpy()
-            fr = self._freqs().numpy()
-            cfg = _lib.MlpConfig(self.input_dim, self.out_dim, self.hidden_size, self.hidden_layers, self.emb_size,
-                                 int(self._temperature))
-            h = ctypes.c_void_p()
-            with torch.cuda.device(device):
-                _lib.check(_lib.lib().pita_mlp_create(ctypes.byref(h), ctypes.byref(cfg),
-                                                      flat.ctypes.data_as(ctypes.c_void_p), flat.size,
-                                                      fr.ctypes.data_as(ctypes.c_void_p)), "pita_mlp_create")
-            self._handle, self._handle_key = h, key
-        return self._handle
+    def _create_handle(self, flat):
+        fr = self._freqs().numpy()
+        cfg = _lib.MlpConfig(self.input_dim, self.out_dim, self.hidden_size, self.hidden_layers, self.emb_size,
+                             int(self._temperature))
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().pita_mlp_create(ctypes.byref(h), ctypes.byref(cfg), flat.ctypes.data_as(ctypes.c_void_p),
+                                              flat.size, fr.ctypes.data_as(ctypes.c_void_p)), "pita_mlp_create")
+        return h
 
-    def __getstate__(self):
-        """The native handle is a per-process device resource: copies / pickles start without one."""
-        state = self.__dict__.copy()
-        state["_handle"], state["_handle_key"] = None, None
-        state.pop("_tensor_list", None)
-        return state
-
-    def _release(self):
-        if self._handle is not None:
-            _lib.lib().pita_mlp_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _run(self, t, x, beta):
-        x = _lib.dev_tensor(x, "x")
-        B = x.shape[0]
-        t = _lib.dev_tensor(t, "t").reshape(-1).expand(B).contiguous()
-        if beta is not None:
-            beta = _lib.dev_tensor(beta, "beta").reshape(-1).expand(B).contiguous()
-        out = torch.empty(B, self.out_dim, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().pita_mlp_forward(self._native(x.device), t.data_ptr(), x.data_ptr(), _lib.ptr(beta),
-                                               out.data_ptr(), B, _lib.stream_ptr(x.device)), "pita_mlp_forward")
-        return out
+    def _conditions_on_beta(self):
+        return self._temperature
 
     # ------------------------------------------------------------------ derivatives of the EDM denoiser (debiased regime)
     # Same contracts as EGNN_dynamics.jvp / vjp / jacobian_trace; one launch each (csrc/mlp_jac_kernel.hip).
-    def _prep(self, h_t, x_t, beta):
-        x_t = _lib.dev_tensor(x_t, "x_t")
-        B = x_t.shape[0]
-        h_t = _lib.dev_tensor(h_t, "h_t").reshape(-1).expand(B).contiguous()
-        b = _as_batch(beta, B, x_t.device) if self._temperature else None
-        return h_t, x_t, b
-
     def jvp(self, h_t, x_t, beta, vx=None, direction=-1, vh=None, want_primal=True, want_tangent=True, dot_out=None,
             dot_col=0, diag_acc=None):
         """(D, dD): the denoiser D_theta(h, x) and its forward-mode derivative along ONE tangent direction:
         dD = J_x D . vx + dD/dh . vh.  ``vx``: [B, D] tensor, or None for the unit direction ``direction`` of
         every walker (-1 = zero).  ``vh``: [B] tensor or None.  Optional in-kernel reductions:
         ``dot_out[:, dot_col] = <x, dD>`` and ``diag_acc += dD[:, direction]`` (pita_mlp_jvp)."""
-        h_t, x_t, b = self._prep(h_t, x_t, beta)
-        B = x_t.shape[0]
-        if vx is not None:
-            vx = _lib.dev_tensor(vx, "vx")
-        if vh is not None:
-            vh = _lib.dev_tensor(vh, "vh").reshape(-1).expand(B).contiguous()
-        out = torch.empty_like(x_t) if want_primal else None
-        dout = torch.empty_like(x_t) if want_tangent else None
-        stride = 1
-        if dot_out is not None:
-            assert dot_out.is_cuda and dot_out.dtype == torch.float32 and dot_out.is_contiguous()
-            stride = dot_out.shape[1] if dot_out.dim() == 2 else 1
-        _lib.check(_lib.lib().pita_mlp_jvp(self._native(x_t.device), h_t.data_ptr(), x_t.data_ptr(), _lib.ptr(b),
-                                           _lib.ptr(vx), int(direction), _lib.ptr(vh), _lib.ptr(out), _lib.ptr(dout),
-                                           _lib.ptr(dot_out), stride, int(dot_col), _lib.ptr(diag_acc), B,
-                                           _lib.stream_ptr(x_t.device)), "pita_mlp_jvp")
-        return out, dout
+        return self._jvp_call("pita_mlp_jvp", h_t, x_t, beta, vx, direction, vh, want_primal, want_tangent, dot_out,
+                              dot_col, diag_acc)
 
     def jacobian(self, h_t, x_t, beta, cot=None, want_denoiser=False, want_trace=False, want_vjp=False,
                  want_dot_h=False, want_h_parts=False):
         """Every requested derivative of D_theta(h, x) from ONE launch of pita_mlp_jacobian, as a dict with the keys
         ``D`` [B, D], ``trace`` [B], ``vjp`` = J_x D^T cot [B, D], ``dot_h`` = <cot, dD/dh> [B] and ``h_parts`` [B, 2]
         (``cot`` default: x)."""
-        h_t, x_t, b = self._prep(h_t, x_t, beta)
+        h_t, x_t, b = self._inputs(h_t, x_t, beta)
         B = x_t.shape[0]
         if cot is not None:
             cot = _lib.dev_tensor(cot, "cot")
@@ -193,17 +135,12 @@ class _HipMLP(nn.Module):
 class MyMLP(_HipMLP):
     def forward(self, t, x, x_self_cond=False):
         """The third positional argument swallows beta exactly like the reference (mlp.py:244)."""
-        return self._run(t, x, None)
+        return self._forward_call("pita_mlp_forward", t, x, None, out_dim=self.out_dim)
 
 
 class MyMLPTemperature(_HipMLP):
     _temperature = True
 
     def forward(self, t, x, beta):
-        return self._run(t, x, beta)
+        return self._forward_call("pita_mlp_forward", t, x, beta, out_dim=self.out_dim)
 
-
-def _as_batch(v, B, device):
-    if isinstance(v, torch.Tensor):
-        return _lib.dev_tensor(v.to(device), "beta").reshape(-1).expand(B).contiguous()
-    return torch.full((B,), float(v), device=device, dtype=torch.float32)

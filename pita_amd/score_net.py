@@ -1,13 +1,15 @@
 """EDM-preconditioned score / denoiser wrappers with the interface of pita/src/models/components/score_net.py.
 
-Dispatch: a backbone that exposes ``edm`` (the HIP EGNN) evaluates preconditioning and network in ONE kernel launch;
-any other backbone module (``forward(t, x, beta)``, e.g. the HIP MLP or a user plug-in) is wrapped by two small HIP
-kernels -- ``pita_edm_scale_input`` before it and ``pita_edm_combine`` after it (score_net.py:26-38).
+Dispatch: a backbone that exposes ``edm`` evaluates preconditioning and network in ONE kernel launch; any other
+backbone module (``forward(t, x, beta)``, e.g. the HIP MLP or a user plug-in) is wrapped by two small HIP kernels --
+``pita_edm_scale_input`` before it and ``pita_edm_combine`` after it (score_net.py:26-38).  What ``edm`` must return
+and which backbones offer it: the protocol table in ``_backbone.py``.
 """
 import torch
 from torch import nn
 
 from . import _lib
+from ._backbone import as_batch
 
 
 def edm_coefficients(h_t):
@@ -28,11 +30,7 @@ class _Preconditioned(nn.Module):
     def reinitialize(self, model):
         self.model = model
 
-    @staticmethod
-    def _batch(v, B, device):
-        if not isinstance(v, torch.Tensor):
-            return torch.full((B,), float(v), device=device, dtype=torch.float32)
-        return _lib.dev_tensor(v.to(device), "per-walker scalar").reshape(-1).expand(B).contiguous()
+    _batch = staticmethod(as_batch)
 
     def _wrapped(self, h_t, x_t, beta, want_D, want_score, precondition_beta):
         x = _lib.dev_tensor(x_t, "x_t")

@@ -15,7 +15,8 @@
   tangent-only launches that stream it).  MLP backbones (MyMLP / MyMLPTemperature): one forward-mode launch per net
   (pita_mlp_jacobian, csrc/mlp_jac_kernel.hip) whose D unit tangents and h tangent share the primal's weight stream
   and give J_x D^T x, <x, dD/dh> and the trace in-kernel.  Per step; the clamp is pita_quantile_clamp per inference
-  chunk.  Any backbone with ``jvp`` (and optionally ``vjp`` / ``jacobian_trace``) runs this regime.
+  chunk.  Any backbone with ``jvp`` (and optionally ``vjp`` / ``jacobian_trace``) runs this regime; the attributes
+  probed for, what each must return and which backbones offer them: the protocol table in ``_backbone.py``.
   ``VEReverseSDE(divergence="hutchinson", n_probes=K)`` replaces the exact trace by the Hutchinson estimate the
   reference's utils.py ships beside ``compute_divergence_exact``: mean over K Rademacher probes of <v, J_x D v>
   (``jacobian_trace_estimate`` on the wide EGNN: pita_egnn_wide_trace_probes, one call; K ``jvp`` launches elsewhere).
