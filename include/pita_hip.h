@@ -289,7 +289,15 @@ typedef struct {
  * fewer where the device's per-block LDS cannot hold the interaction tables (bonded terms, the dense pair table,
  * per-atom lists) plus that many walkers' working set; where not even one walker fits, PITA_EUNSUPPORTED with the bytes
  * needed and available.  A handle that exists is therefore taken by pita_ff_logp_force, pita_ff_descent and
- * pita_ff_mala (which lives in the descent's footprint), and a walker's result does not depend on the plan. */
+ * pita_ff_mala (which lives in the descent's footprint), and a walker's result does not depend on the plan.
+ * Measured capacity: 256 is the bound of the thread mapping, not what the LDS holds.  The dense pair table grows as
+ * n_atoms^2 (24 B per pair: 100 KB at 92 atoms), so with amber-shaped tables (about one bond, 1.7 angles and 4.8 torsion
+ * terms per atom, GB on) and the 163 840 B per block of gfx950 the largest peptide chain accepted is
+ * ACE-(ALA)7-GLY-NME, 89 atoms (159 868 B for one walker per block), and the first one refused is ACE-(ALA)8-NME,
+ * 92 atoms (169 104 B): PITA_EUNSUPPORTED.  Walkers per block at that limit: 11 at 22 atoms, 3 at 64 and 65, 2 at 73,
+ * 1 from 85 on (tests/_ff_shapes.py restates the accounting; tests/test_ff_shapes_gpu.py runs every step of it).
+ * Systems with fewer bonded terms reach further, none past 113 atoms: the pair table and one walker's arrays alone
+ * exceed that limit from 114 atoms on. */
 int pita_ff_create(pita_ff_t** out, const pita_ff_config* cfg);
 int pita_ff_destroy(pita_ff_t* ff);
 int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, float* force /*nullable*/, int64_t B, void* stream);

@@ -103,7 +103,11 @@ class ForceFieldEnergy(BaseMoleculeEnergy):
         tors_idx[nt,4], tors_par[nt,3], charge[n], sigma[n], epsilon[n], exc_idx[ne,2], exc_par[ne,3]; optional
         gb_radius[n], gb_scale[n] switch the GB-OBC1 implicit solvent on (OpenMM GBSAOBCForce parameters).
         Up to 256 atoms (alanine di-, tri- and tetra-peptide and beyond): the kernel handle takes as many walkers per
-        block as the device's LDS holds with these tables, the same for ``__call__``, ``fused_descent`` and ``fused_mala``."""
+        block as the device's LDS holds with these tables, the same for ``__call__``, ``fused_descent`` and ``fused_mala``.
+        256 is the bound of the thread mapping; what the LDS holds is less, because the dense pair table grows as n^2.
+        Measured with amber-shaped peptide tables at 163 840 B of LDS per block (gfx950): the largest chain accepted is
+        ACE-(ALA)7-GLY-NME, 89 atoms, the first refused is ACE-(ALA)8-NME, 92 atoms (169 104 B for one walker):
+        ``pita_ff_create`` then fails with PITA_EUNSUPPORTED and the bytes needed and available."""
         assert spatial_dim == 3
         super().__init__(dimensionality=3 * n_particles, n_particles=n_particles, spatial_dim=3, data_path=None,
                          device=device, is_molecule=is_molecule, temperature=temperature, should_normalize=False,

@@ -48,6 +48,15 @@ SEQUENCES = {
     "ala3": ["NALA", "ALA", "CALA"],                                      # zwitterionic tri-alanine, 33 atoms
     "ala4": ["ACE", "ALA", "ALA", "ALA", "NME"],                          # ACE-(ALA)3-NME, 42 atoms
     "chain64": ["NALA", "ALA", "ALA", "GLY", "GLY", "GLY", "CALA"],       # capacity test, 64 atoms
+    # tests/_ff_shapes.py: both sides of every step of the launch plan (walkers per block), up to the first chain refused
+    "ace_nme": ["ACE", "NME"],                                            # 12 atoms
+    "gly1": ["ACE", "GLY", "NME"],                                        # 19 atoms: 13 walkers = 247 threads
+    "chain65": ["NALA"] + 6 * ["GLY"] + ["CALA"],                         # 65 atoms: 3 per block, set by the threads
+    "chain73": ["ACE"] + 4 * ["ALA"] + 3 * ["GLY"] + ["NME"],             # 73 atoms: 2 per block, 256 / n gives 3
+    "chain85": ["ACE", "ALA"] + 9 * ["GLY"] + ["NME"],                    # 85 atoms: 1 per block, 256 / n gives 3
+    "chain86": ["ACE"] + 6 * ["ALA"] + 2 * ["GLY"] + ["NME"],             # 86 atoms: 1 per block, 256 / n gives 2
+    "chain89": ["ACE"] + 7 * ["ALA"] + ["GLY", "NME"],                    # 89 atoms: the largest accepted (160 KB of LDS)
+    "chain92": ["ACE"] + 8 * ["ALA"] + ["NME"],                           # 92 atoms: refused, 169 104 B
 }
 # equilibrium bond lengths (nm) and force constants (kJ/mol/nm^2) by element pair
 _BOND = {("C", "C"): (0.1522, 2.653e5), ("C", "H"): (0.1090, 2.845e5), ("C", "N"): (0.1335, 4.101e5),
@@ -111,8 +120,18 @@ def _geometry(n, bonds, elem, prio, rng):
 def peptide(name, seed=0):
     """(tables, positions in nm) of the named system (``SEQUENCES``); tables as ``tests._synthetic.synthetic_peptide``
     plus gb_radius / gb_scale.  Deterministic in ``seed``."""
-    rng = np.random.default_rng(seed)
-    atoms, bonds, carbonyl_c, amide_n = _topology(SEQUENCES[name])
+    return _system(*_topology(SEQUENCES[name]), np.random.default_rng(seed))
+
+
+def molecule(atoms, bonds, seed=0):
+    """(tables, positions in nm) of a hand-written bond graph: ``atoms`` = [(name, type of ``_TYPES``, charge)],
+    ``bonds`` = [(i, j)] between elements that ``_BOND`` pairs; geometry and parameters as ``peptide`` sets them (every
+    angle and proper of the graph, exclusions and scaled 1-4 pairs, GB by type), no impropers.  Tables without a term
+    are empty arrays of the right width."""
+    return _system(list(atoms), [tuple(b) for b in bonds], [], [], np.random.default_rng(seed))
+
+
+def _system(atoms, bonds, carbonyl_c, amide_n, rng):
     n = len(atoms)
     elem = [_TYPES[ty][0] for _, ty, _ in atoms]
     nbr = {i: set() for i in range(n)}
@@ -146,8 +165,9 @@ def peptide(name, seed=0):
         h = next(i for i in nbr[nn] if elem[i] == "H")
         others = sorted(nbr[nn] - {h})
         tors_idx.append((others[0], others[1], nn, h)); tors_par.append((2.0, np.pi, 4.6024))
-    t = dict(bond_idx=np.array(bonds), bond_par=np.array(bond_par), angle_idx=np.array(angles), angle_par=np.array(angle_par),
-             tors_idx=np.array(tors_idx), tors_par=np.array(tors_par),
+    t = dict(bond_idx=np.array(bonds), bond_par=np.array(bond_par), angle_idx=np.array(angles, dtype=int).reshape(-1, 3),
+             angle_par=np.array(angle_par, dtype=float).reshape(-1, 2), tors_idx=np.array(tors_idx, dtype=int).reshape(-1, 4),
+             tors_par=np.array(tors_par, dtype=float).reshape(-1, 3),
              charge=np.array([q for _, _, q in atoms]), sigma=np.array([_TYPES[ty][1] for _, ty, _ in atoms]),
              epsilon=np.array([_TYPES[ty][2] for _, ty, _ in atoms]))
     # exceptions: 1-2 and 1-3 pairs excluded, 1-4 pairs scaled (Coulomb 1/1.2, LJ 1/2)

@@ -7,7 +7,9 @@ import pytest
 from tests._peptides import SEQUENCES, peptide, peptide_system_xml
 
 # system -> (atoms, minimum bonds, angles, torsion terms): amber14 ACE-ALA-NME, zwitterionic ALA3, ACE-ALA3-NME
-MIN_TERMS = {"ala2": (22, 21, 36, 64), "ala3": (33, 32, 57, 100), "ala4": (42, 41, 72, 130), "chain64": (64, 63, 0, 0)}
+MIN_TERMS = {"ala2": (22, 21, 36, 64), "ala3": (33, 32, 57, 100), "ala4": (42, 41, 72, 130), "chain64": (64, 63, 0, 0),
+             **{k: (n, n - 1, 0, 0) for k, n in dict(ace_nme=12, gly1=19, chain65=65, chain73=73, chain85=85, chain86=86,
+                                                      chain89=89, chain92=92).items()}}
 
 
 @pytest.mark.parametrize("name", sorted(SEQUENCES))
