@@ -698,6 +698,23 @@ int pita_adaptive_resample(const float* logits, int64_t B, double u0, double the
 /* 1 when B takes the one-launch path, 0 for the gated multi-pass path */
 int pita_adaptive_resample_single_launch(int64_t B);
 
+/* n_pop independent populations of pop_size walkers each, one event per population, in ONE launch: block p owns rows
+ * [p * pop_size, (p + 1) * pop_size) of every array and does exactly what
+ *   pita_adaptive_resample(logits + p * pop_size, pop_size, u0_dev[p], theta, ...)
+ * does: stats row p (device double[n_pop, 6]), resampled[p] and n_unique[p] (nullable) are that call's bits, and
+ * ids[p * pop_size + k] = p * pop_size + (that call's ids[k]) -- GLOBAL rows, so pita_gather_rows takes the vector as it
+ * is.  theta >= 1 is the fixed schedule (every population resamples).  logw_next (nullable, device [n_pop * pop_size]):
+ * 0 where population p resampled, logits where it did not; it may be `logits` itself (a block reads its slice into LDS
+ * before it writes anything).  Blocks share nothing and there are no atomics: a population's bits depend neither on n_pop
+ * nor on p.  u0_dev: DEVICE double[n_pop], each in [0, 1) (not checked: the host never reads it).  theta in [0, 1].
+ * 1 <= pop_size <= 2 048, what one block holds in LDS (pita_adaptive_resample_single_launch); a larger pop_size is
+ * PITA_EUNSUPPORTED.  All argument checks run before any device call.  workspace: 8-byte aligned, at least
+ * pita_population_resample_workspace_bytes bytes (the event needs no scratch; the size is never 0). */
+size_t pita_population_resample_workspace_bytes(int64_t n_pop, int64_t pop_size);
+int pita_population_resample(const float* logits, int64_t n_pop, int64_t pop_size, const double* u0_dev, double theta,
+                             int64_t* ids, int64_t* n_unique, double* stats, int* resampled, float* logw_next,
+                             void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

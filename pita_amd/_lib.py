@@ -158,6 +158,9 @@ _PROTOS = {
     "pita_adaptive_resample": (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
     "pita_adaptive_resample_single_launch": (c_int, [c_int64]),
+    "pita_population_resample_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "pita_population_resample": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

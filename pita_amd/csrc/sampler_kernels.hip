@@ -572,11 +572,13 @@ static_assert(AR_MAX_B % RS_E == 0 && AR_MAX_B <= 65536 && AR_MAX_B * 6 + 16384 
 
 __host__ __device__ inline size_t ar_val_bytes(long long B) { return ((size_t)B * 4 + 7) & ~(size_t)7; }
 
-__global__ void __launch_bounds__(AR_T) adaptive_resample_block_kernel(const float* __restrict__ logits, int B, double u0,
-                                                                       double theta, long long* __restrict__ ids,
-                                                                       long long* __restrict__ n_unique,
-                                                                       double* __restrict__ stats,
-                                                                       int* __restrict__ resampled) {
+// The event of one block: the body of adaptive_resample_block_kernel (one population: id_base 0, no logw_next) and of
+// population_resample_kernel (block p: its slice of every array, id_base = p * B).  ids are written as parent + id_base;
+// logw_next (nullable) gets 0 where the event resamples and the log-weights where not, from the LDS copy -- every read of
+// `logits` precedes the first barrier and every write follows it, so logw_next may be logits.  Called by all AR_T threads.
+__device__ __forceinline__ void adaptive_resample_block(const float* logits, int B, double u0, double theta, long long* ids,
+                                                        long long id_base, long long* n_unique, double* stats,
+                                                        int* resampled, float* logw_next) {
   extern __shared__ double ar_lds[];
   __shared__ StatsLds L;
   __shared__ double part[AR_G][RS_T], red[AR_G][RS_T / 64], bsum[AR_MAX_VB], bw[AR_MAX_VB];
@@ -589,10 +591,14 @@ __global__ void __launch_bounds__(AR_T) adaptive_resample_block_kernel(const flo
   const int flag = logweight_stats_block(val, B, theta, stats, L);
   if (tid == 0) *resampled = flag;
   if (!flag) {  // uniform: every thread folded the same partials
-    for (int i = tid; i < B; i += AR_T) ids[i] = i;
+    for (int i = tid; i < B; i += AR_T) ids[i] = id_base + i;
+    if (logw_next)
+      for (int i = tid; i < B; i += AR_T) logw_next[i] = val[i];
     if (tid == 0 && n_unique) *n_unique = B;
     return;
   }
+  if (logw_next)
+    for (int i = tid; i < B; i += AR_T) logw_next[i] = 0.0f;
   const int nb = (B + RS_E - 1) / RS_E;
   for (int v0 = 0; v0 < nb; v0 += AR_G) {  // A
     const float m = rs_pass_max(val, B, v0 + g, t, redf[g]);
@@ -619,13 +625,33 @@ __global__ void __launch_bounds__(AR_T) adaptive_resample_block_kernel(const flo
   const float invB = (float)(1.0 / (double)B);
   for (int k = tid; k < B; k += AR_T) {  // E
     const long long id = rs_search(val, B, u0, invB, k);
-    ids[k] = id;
+    ids[k] = id_base + id;
     par[k] = (unsigned short)id;
   }
   __syncthreads();
   long long runs = 0;
   count_runs_block(par, B, &runs);  // thread 0 holds the count
   if (tid == 0 && n_unique) *n_unique = runs;
+}
+
+__global__ void __launch_bounds__(AR_T) adaptive_resample_block_kernel(const float* __restrict__ logits, int B, double u0,
+                                                                       double theta, long long* __restrict__ ids,
+                                                                       long long* __restrict__ n_unique,
+                                                                       double* __restrict__ stats,
+                                                                       int* __restrict__ resampled) {
+  adaptive_resample_block(logits, B, u0, theta, ids, 0, n_unique, stats, resampled, nullptr);
+}
+
+// P independent populations of S <= AR_MAX_B walkers, one event each, in ONE launch: block p owns rows [p S, (p + 1) S) and
+// runs the one-population body on them with its own uniform u0[p].  Blocks share nothing (no atomics, no scratch), so a
+// population's bits depend neither on n_pop nor on p; the ids are global rows (p S + parent), ready for gather_rows_kernel.
+// No __restrict__: logw_next may be logits.
+__global__ void __launch_bounds__(AR_T) population_resample_kernel(const float* logits, int S, const double* __restrict__ u0,
+                                                                   double theta, long long* ids, long long* n_unique,
+                                                                   double* stats, int* resampled, float* logw_next) {
+  const long long p = blockIdx.x, base = p * S;
+  adaptive_resample_block(logits + base, S, u0[p], theta, ids + base, base, n_unique ? n_unique + p : nullptr,
+                          stats + 6 * p, resampled + p, logw_next ? logw_next + base : nullptr);
 }
 
 // ---- the gated multi-pass event (B > AR_MAX_B): logweight_stats_kernel writes the flag, the passes of
@@ -891,6 +917,28 @@ extern "C" int pita_adaptive_resample(const float* logits, int64_t B, double u0,
   if (n_unique)
     hipLaunchKernelGGL(count_runs_gated_kernel, dim3(1), dim3(1024), 0, s, gate, (const long long*)ids, (long long)B,
                        (long long*)n_unique);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// every population is the one-launch event of its block: no scratch (8 bytes so that the pointer is never null)
+extern "C" size_t pita_population_resample_workspace_bytes(int64_t, int64_t) { return 8; }
+
+extern "C" int pita_population_resample(const float* logits, int64_t n_pop, int64_t pop_size, const double* u0_dev,
+                                        double theta, int64_t* ids, int64_t* n_unique, double* stats, int* resampled,
+                                        float* logw_next, void* workspace, void* stream) {
+  PITA_REQUIRE(n_pop >= 1 && n_pop <= 0x7fffffffLL, "pita_population_resample: n_pop must be in [1, 2^31) (got %lld)",
+               (long long)n_pop);
+  PITA_REQUIRE(pop_size >= 1, "pita_population_resample: pop_size must be at least 1 (got %lld)", (long long)pop_size);
+  if (pop_size > AR_MAX_B)
+    return fail(PITA_EUNSUPPORTED, "pita_population_resample: pop_size %lld exceeds the %d walkers one block holds in LDS",
+                (long long)pop_size, AR_MAX_B);
+  PITA_REQUIRE(logits && u0_dev && ids && stats && resampled && workspace, "pita_population_resample: null argument");
+  PITA_REQUIRE(theta >= 0.0 && theta <= 1.0, "pita_population_resample: theta must be in [0, 1] (got %g)", theta);
+  PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_population_resample: workspace must be 8-byte aligned");
+  hipLaunchKernelGGL(population_resample_kernel, dim3((unsigned)n_pop), dim3(AR_T),
+                     ar_val_bytes(pop_size) + 2 * (size_t)pop_size, (hipStream_t)stream, logits, (int)pop_size, u0_dev, theta,
+                     (long long*)ids, (long long*)n_unique, stats, resampled, logw_next);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

@@ -16,6 +16,9 @@ How the work is laid out on MI355X (differences from the reference are deliberat
     distinct parents it needs (_Comm.exchange_rows);
   * noise is Philox4x32-10 keyed by (seed, GLOBAL walker index, step): the result does not depend
     on the number of GPUs.  ``noise=`` injects recorded normals for parity tests.
+  * ``populations=P`` (an extension): the batch is P independent populations of at most 2 048 walkers, each resampled
+    on its own in one launch per event (pita_population_resample); events are rank-local, the log-weights and the event
+    log are gathered once after the loop.
 ``sde_terms_all`` has N entries like the reference's (:150,:212).  By default each field is a ``TermStats`` (sum,
 sum of squares, count over the global batch, reduced on the device) that answers ``.mean()`` / ``.std()`` -- the only
 things the reference's callers ever ask of these tensors (energytemp_module.py:938-945,1132-1143);
@@ -30,7 +33,7 @@ from . import _lib
 from .data_utils import remove_mean
 from .metrics import logweight_stats
 from .sdes import SDETerms, TermStats, VEReverseSDE  # noqa: F401
-from .utils import gather_rows, sample_cat_sys, sample_cat_sys_adaptive
+from .utils import MAX_POPULATION_SIZE, gather_rows, sample_cat_sys, sample_cat_sys_adaptive, sample_cat_sys_populations
 
 
 def _scalar(v):
@@ -155,6 +158,17 @@ class _Comm:
                 torch.distributed.broadcast(u, 0)
         return u
 
+    def broadcast_host(self, t):
+        """Rank 0's host tensor ``t`` on every rank (the uniforms of a run with ``populations``: once, before the loop)."""
+        if self.world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            if torch.distributed.get_backend() == "nccl":
+                td = t.cuda()
+                torch.distributed.broadcast(td, 0)
+                t = td.cpu()
+            else:
+                torch.distributed.broadcast(t, 0)
+        return t
+
     def exchange_rows(self, x, ids, Bl):
         """Rows ``ids[rank*Bl:(rank+1)*Bl]`` of the batch whose shards are the ranks' ``x`` [Bl, D]; ``ids`` [world*Bl]
         are the parents of a global systematic resampling: identical on every rank, non-decreasing up to the cyclic
@@ -224,12 +238,14 @@ def _host_counts(counts):
 
 class _EventLog:
     """Per-step outputs of the adaptive resampling events of one run (``ess_threshold``), preallocated on the device:
-    the kernel of step s writes row s, the host reads everything once after the loop (``finish``)."""
+    the kernel of step s writes row s, the host reads everything once after the loop (``finish``).  With ``P`` (a run
+    with ``populations``) every row has one column per population of ``B`` walkers."""
 
-    def __init__(self, N, B, device):
-        self.stats = torch.full((N, 6), float("nan"), dtype=torch.float64, device=device)
-        self.flags = torch.zeros(N, dtype=torch.int32, device=device)
-        self.counts = torch.full((N,), B, dtype=torch.int64, device=device)
+    def __init__(self, N, B, device, P=None):
+        cols = () if P is None else (P,)
+        self.stats = torch.full((N,) + cols + (6,), float("nan"), dtype=torch.float64, device=device)
+        self.flags = torch.zeros((N,) + cols, dtype=torch.int32, device=device)
+        self.counts = torch.full((N,) + cols, B, dtype=torch.int64, device=device)
 
     def row(self, step):
         return self.flags[step], self.stats[step], self.counts[step]
@@ -242,6 +258,84 @@ class _EventLog:
         tail = logweight_stats(final_logweights)["log_mean_weight"]
         return {"ess": h[:, 2].copy(), "ess_fraction": h[:, 3].copy(), "log_mean_weight": lmw, "resampled": resampled,
                 "log_z": float(lmw[resampled].sum()) + tail}
+
+
+def population_layout(Bg, world, populations, batch_size):
+    """``(S, populations per rank, clamp chunk)`` of a run of ``Bg`` walkers in ``populations`` independent populations
+    over ``world`` ranks: S = Bg / populations walkers each, whole populations per rank, and the 0.9-quantile clamp of the
+    debiased drift over chunks of ``min(batch_size or S, S)`` walkers, which must tile a population.  ValueError where
+    the walkers do not split evenly, a population exceeds what one block resamples (2 048), populations would straddle
+    ranks or the clamp chunks would straddle populations."""
+    Bg, world, P = int(Bg), int(world), int(populations)
+    if P < 1:
+        raise ValueError(f"populations must be at least 1, got {P}")
+    if Bg < P or Bg % P != 0:
+        raise ValueError(f"{Bg} walkers do not split into {P} populations of equal size")
+    S = Bg // P
+    if S > MAX_POPULATION_SIZE:
+        raise ValueError(f"a population of {S} walkers exceeds the limit of {MAX_POPULATION_SIZE} (one block per population)")
+    if P % world != 0:
+        raise ValueError(f"{P} populations do not split over {world} ranks: populations never straddle ranks")
+    chunk = S if not batch_size else min(int(batch_size), S)
+    if S % chunk != 0:
+        raise ValueError(f"batch_size {batch_size} does not tile a population of {S} walkers (clamp chunks)")
+    return S, P // world, chunk
+
+
+class _PopulationRun:
+    """One run with ``populations=P``: the layout, this rank's columns of the run's uniforms [events, P] on the device
+    (drawn or taken once, rank 0's on every rank) and the event log, one row per step and one more for
+    ``resample_at_end``.  Every event is rank-local: one pita_population_resample launch and the row gather."""
+
+    def __init__(self, comm, Bg, P, batch_size, N, n_events, resample_u, device):
+        self.P, self.N = P, N
+        self.S, self.Pl, self.chunk = population_layout(Bg, comm.world, P, batch_size)
+        if resample_u is None:
+            u = torch.rand((n_events, P), dtype=torch.float64)
+        else:
+            u = torch.as_tensor(resample_u, dtype=torch.float64).detach().cpu().clone()
+            if tuple(u.shape) != (n_events, P):
+                raise ValueError(f"resample_u has shape {tuple(u.shape)}, expected (events, populations) = {(n_events, P)}")
+            if not bool(((u >= 0.0) & (u < 1.0)).all()):
+                raise ValueError("resample_u must lie in [0, 1)")
+        u = comm.broadcast_host(u)
+        lo = comm.rank * self.Pl
+        self.u = u[:, lo:lo + self.Pl].contiguous().to(device)
+        self.log = _EventLog(N + 1, self.S, device, self.Pl)
+        self.next_event = 0
+
+    def event(self, x, a, theta, row):
+        """(x, a) after the event whose outputs go to row ``row`` of the log; ``a``: this rank's log-weights."""
+        u = self.u[self.next_event]
+        self.next_event += 1
+        ids, _, _, _, a_next = sample_cat_sys_populations(a, self.Pl, 1.0 if theta is None else theta, u,
+                                                          out=self.log.row(row))
+        return gather_rows(x, ids), a_next
+
+    def gather_rows_of_ranks(self, comm, t):
+        """[R, Bl, ...] of every rank -> [R, Bg, ...] in population order (one all-gather)."""
+        if comm.world == 1:
+            return t
+        g = comm.all_gather(t.contiguous()).reshape((comm.world,) + tuple(t.shape))
+        return g.transpose(0, 1).reshape((t.shape[0], comm.world * t.shape[1]) + tuple(t.shape[2:]))
+
+    def finish(self, comm, final_logweights, synthetic=()):
+        """``(last_weight_stats, counts per step [N + 1] as python ints)``; the log of every rank is read once.
+        ``synthetic``: due steps whose events were skipped on the host because the weights are identically zero."""
+        L = self.log
+        packed = torch.cat([L.stats, L.flags[..., None].double(), L.counts[..., None].double()], dim=-1)
+        h = self.gather_rows_of_ranks(comm, packed).cpu().numpy()  # [N + 1, P, 8]
+        N = self.N
+        st, resampled = h[:N, :, :6].copy(), h[:N, :, 6] != 0
+        for s in synthetic:  # ESS = S, mean weight 1, not resampled
+            st[s, :, 1], st[s, :, 2], st[s, :, 3] = 0.0, float(self.S), 1.0
+        tail = logweight_stats(final_logweights.reshape(self.P, self.S))["log_mean_weight"]
+        lmw = st[:, :, 1]
+        # per population the sum _EventLog.finish takes for one: the same numbers in the same order
+        log_z = np.array([lmw[resampled[:, p], p].sum() for p in range(self.P)], np.float64) + tail
+        stats = {"ess": st[:, :, 2].copy(), "ess_fraction": st[:, :, 3].copy(), "log_mean_weight": lmw.copy(),
+                 "resampled": resampled, "n_unique": h[:N, :, 7].astype(np.int64), "log_z": log_z, "populations": self.P}
+        return stats, [int(c) for c in h[:, :, 7].sum(1)]
 
 
 def _terms_from_stats(st4, st8, n_elem, n_walk, computed, debiased):
@@ -268,11 +362,27 @@ class WeightedSDEIntegrator:
                  partial_annealing_factor_schedule=None, reverse_time=True, diffusion_scale=1.0, time_range=1.0,
                  resampling_interval=-1, num_negative_time_steps=100, post_mcmc_steps=100, adaptive_mcmc=False,
                  batch_size=None, no_grad=True, resample_at_end=False, dt_negative_time=1e-4, do_langevin=False,
-                 should_mean_free=True, seed=0, record_terms=False, verbose=False, ess_threshold=None):
+                 should_mean_free=True, seed=0, record_terms=False, verbose=False, ess_threshold=None,
+                 populations=None):
         """``ess_threshold``: None (the reference's fixed schedule: every due event resamples) or a fraction in [0, 1] --
         a due event then resamples only when the effective sample size of the log-weights is at most
         ``ess_threshold * batch``, decided on the device (``sample_cat_sys_adaptive``; an extension the reference does
-        not have), and ``last_weight_stats`` holds the per-event diagnostics of the last run."""
+        not have), and ``last_weight_stats`` holds the per-event diagnostics of the last run.
+
+        ``populations``: None (one population: the whole batch, exactly the launches and bits of before) or P >= 1 -- the
+        batch is P independent populations of S = batch / P <= 2 048 walkers, rows [p S, (p + 1) S) being population p
+        from the first to the last step and in everything returned.  Each population has its own ESS, decision, uniform,
+        systematic resampling, distinct-parent count, quantile clamp and ``log_z``; every event is one launch
+        (``sample_cat_sys_populations``) plus the row gather on the rank's own walkers, with no collective, because
+        populations never straddle ranks.  ``resample_u`` is then [events, P] (event-major, ``resample_at_end`` last),
+        ``last_weight_stats`` is filled whatever ``ess_threshold`` is, its per-event arrays are [N, P] and ``log_z`` is
+        [P].  The one coupling between populations: an adaptive MALA step size adapts to the acceptance rate over the
+        whole batch."""
+        if populations is not None:
+            if isinstance(populations, bool) or not isinstance(populations, (int, np.integer)) or populations < 1:
+                raise ValueError(f"populations must be None or an int >= 1, got {populations!r}")
+            populations = int(populations)
+        self.populations = populations
         if ess_threshold is not None:
             try:
                 ok = 0.0 <= float(ess_threshold) <= 1.0  # NaN fails both comparisons
@@ -339,7 +449,9 @@ class WeightedSDEIntegrator:
         """``noise``: optional [N, B, D] device normals (global batch); ``resample_u``: optional
         iterable of float64 uniforms, one per resampling event; ``mala_noise`` [steps, B, D] / ``mala_uniforms``
         [steps, B]: the proposal normals and accept uniforms of the post-processing MALA chain (parity hooks;
-        single rank)."""
+        single rank).  With ``populations=P`` the uniforms of a run are drawn once, before the loop, as
+        ``torch.rand((events, P), dtype=float64)`` (rank 0's on every rank) and ``resample_u`` of that shape replaces
+        them: one row per due event, then one for ``resample_at_end``."""
         if resampling_interval is None:
             resampling_interval = self.resampling_interval
         N = self.num_integration_steps
@@ -357,6 +469,7 @@ class WeightedSDEIntegrator:
         x = x1[off:off + Bl].clone()
         n, d = self._geometry(x, energy_function)
         mean_free = bool(self.should_mean_free)
+        batch_size = self.batch_size  # as given: population_layout tells None from a number
         if self.batch_size is None:
             self.batch_size = Bg
 
@@ -383,17 +496,25 @@ class WeightedSDEIntegrator:
         sde_terms_all = []
         st4 = None if self.record_terms else torch.zeros(N, 4, dtype=torch.float64, device=dev)
         model = self._backbone()
+        pop = None
+        if self.populations is not None:
+            at_end = self.resample_at_end and did_resampling
+            pop = _PopulationRun(comm, Bg, self.populations, batch_size, N, len(events) + int(at_end), resample_u, dev)
+            u_iter = None
         if getattr(self.sde, "debias_inference", False):
             return self._integrate_debiased(x, comm, tab_h, times, noise, key, off, Bl, Bg, n, d, mean_free,
                                             energy_function, annealing_factor_schedule, inverse_temperature,
-                                            resampling_interval, u_iter, mala_draws)
+                                            resampling_interval, u_iter, mala_draws, pop)
 
         due = events
         if self.ess_threshold is not None and self.ess_threshold < 1.0:
             # the weights are identically zero here, so ESS = B at every due event: none of them resamples (decided on the
             # host, no kernel); their uniforms are still drawn, as the fixed schedule would draw them
-            for _ in events:
-                comm.shared_uniform(next(u_iter) if u_iter is not None else None)
+            if pop is not None:
+                pop.next_event += len(events)  # a run's uniforms are drawn up front
+            else:
+                for _ in events:
+                    comm.shared_uniform(next(u_iter) if u_iter is not None else None)
             events = []
         s = start
         bounds = events + [N - 1]
@@ -403,7 +524,11 @@ class WeightedSDEIntegrator:
             self._run_steps(model, x, tab, tab_h, s, stop + 1, noise, key, off, n, d, mean_free, inverse_temperature,
                             sde_terms_all, st4)
             s = stop + 1
-            if stop in events:
+            if stop in events and pop is not None:
+                x, _ = pop.event(x, torch.zeros(Bl, device=dev), 1.0, stop)  # this rank's populations, no collective
+                if mean_free:
+                    x = remove_mean(x, n, d)
+            elif stop in events:
                 a = torch.zeros(comm.world * Bl, device=dev)  # drift_A = 0 in the not-debiased regime
                 u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
                 ids, _ = sample_cat_sys(a.shape[0], a, u)
@@ -420,10 +545,15 @@ class WeightedSDEIntegrator:
 
         if self.resample_at_end and did_resampling:
             x, a_next, n_unique = self._resample_at_end(x, None, comm, times, energy_function, annealing_factor_schedule,
-                                                        inverse_temperature, u_iter, off, Bl)
+                                                        inverse_temperature, u_iter, off, Bl, pop)
+            if pop is not None:
+                a_next = pop.gather_rows_of_ranks(comm, a_next[None])[0]
             logweights = torch.cat([logweights, a_next[None]])
             num_unique_idxs.append(n_unique)
-        if self.ess_threshold is not None:  # zero log-weights at every due event: ESS = B, mean weight 1
+        if pop is not None:
+            self.last_weight_stats, counts = pop.finish(comm, logweights[-1], synthetic=[] if events else due)
+            num_unique_idxs = counts[:len(num_unique_idxs)]
+        elif self.ess_threshold is not None:  # zero log-weights at every due event: ESS = B, mean weight 1
             at = np.zeros(N, dtype=bool)
             at[due] = True
             self.last_weight_stats = {
@@ -437,26 +567,30 @@ class WeightedSDEIntegrator:
         if self.post_mcmc_steps > 0:
             fn = self.metropolis_hastings_mala_adaptive if self.adaptive_mcmc else self.metropolis_hastings_mala
             kw = dict(dt_init=self.dt_negative_time) if self.adaptive_mcmc else {}
+            if pop is not None:
+                kw["keep_order"] = True  # set-aside walkers return to their own rows
             x, acceptance_rate_list = fn(x, energy_function, return_acceptance_rate=True, walker_offset=off, comm=comm,
                                          noise=mala_draws[0], uniforms=mala_draws[1], **kw)
-        x = self._gather_final(x, comm, Bl)  # X1: the only collective on the resampling-free path
+        x = self._gather_final(x, comm, Bl, pop is not None)  # X1: the only collective on the resampling-free path
         return x, logweights, _host_counts(num_unique_idxs), sde_terms_all, acceptance_rate_list
 
     # ------------------------------------------------------------------ debiased regime (per step; section 8(f) N1)
     def _integrate_debiased(self, x, comm, tab_h, times, noise, key, off, Bl, Bg, n, d, mean_free, energy_function,
-                            gamma_schedule, beta, resampling_interval, u_iter, mala_draws=(None, None)):
+                            gamma_schedule, beta, resampling_interval, u_iter, mala_draws=(None, None), pop=None):
         """Feynman-Kac weighted integration (sde_integration.py:131-152,214-297 with sdes.py:151-239): per step the
         drift of x and of the log-weights a per inference chunk, Euler-Maruyama update, window gates, global
         systematic resampling when due.  Resampling is global like the reference's: weights and walkers are
-        all-gathered at every resampling event."""
+        all-gathered at every resampling event.  With ``pop`` (``populations``) every population of the rank resamples on
+        its own: no collective in the loop, the log-weights stay local and are gathered once after it."""
         N = self.num_integration_steps
         dev = x.device
         L = _lib.lib()
         zero_a = torch.zeros(Bl, device=dev)  # never written to: every update of `a` makes a new tensor
-        adaptive = _EventLog(N, comm.world * Bl, dev) if self.ess_threshold is not None else None
+        adaptive = _EventLog(N, comm.world * Bl, dev) if self.ess_threshold is not None and pop is None else None
         a = zero_a
         logweights, num_unique_idxs, sde_terms_all = [], [], []
-        bs = self.batch_size or Bl
+        bs = pop.chunk if pop is not None else self.batch_size or Bl
+        collect = comm.all_gather if pop is None else (lambda v: v)  # a run with populations gathers once, after the loop
         st4 = st8 = None
         if not self.record_terms:
             st4 = torch.zeros(N, 4, dtype=torch.float64, device=dev)
@@ -469,7 +603,7 @@ class WeightedSDEIntegrator:
             row = tab_h[step]
             if step < self.start_resampling_step:  # walkers frozen, weights zero (:278-280)
                 a = zero_a
-                logweights.append(comm.all_gather(a))
+                logweights.append(collect(a))
                 num_unique_idxs.append(Bg)
                 continue
             # one set of launches for the rank's whole shard; the quantile clamp keeps its per-chunk meaning
@@ -497,7 +631,9 @@ class WeightedSDEIntegrator:
             n_unique = Bg
             due = not (resampling_interval == -1 or (step + 1) % resampling_interval != 0
                        or step >= self.end_resampling_step)
-            if due and adaptive is not None:
+            if due and pop is not None:
+                x, a = pop.event(x, a, self.ess_threshold, step)
+            elif due and adaptive is not None:
                 # the event is decided on the device: no host read here, every rank decides alike on the gathered vector;
                 # the uniform is drawn whether or not the event resamples (the fixed schedule's stream)
                 ag = comm.all_gather(a)
@@ -515,7 +651,7 @@ class WeightedSDEIntegrator:
                 a = zero_a
             if mean_free:
                 x = remove_mean(x, n, d)
-            logweights.append(comm.all_gather(a))
+            logweights.append(collect(a))
             num_unique_idxs.append(n_unique)
             if self.record_terms:
                 sde_terms_all.append(terms)
@@ -527,9 +663,13 @@ class WeightedSDEIntegrator:
         did_resampling = resampling_interval != -1 and resampling_interval < N
         if self.resample_at_end and did_resampling:
             x, a_next, n_unique = self._resample_at_end(x, a, comm, times, energy_function, gamma_schedule, beta, u_iter,
-                                                        off, Bl)
+                                                        off, Bl, pop)
             logweights = torch.cat([logweights, a_next[None]])
             num_unique_idxs.append(n_unique)
+        if pop is not None:
+            logweights = pop.gather_rows_of_ranks(comm, logweights)
+            self.last_weight_stats, counts = pop.finish(comm, logweights[-1])
+            num_unique_idxs = counts[:len(num_unique_idxs)]
         if adaptive is not None:
             self.last_weight_stats = adaptive.finish(logweights[-1])
         if self.num_negative_time_steps > 0:
@@ -538,16 +678,19 @@ class WeightedSDEIntegrator:
         if self.post_mcmc_steps > 0:
             fn = self.metropolis_hastings_mala_adaptive if self.adaptive_mcmc else self.metropolis_hastings_mala
             kw = dict(dt_init=self.dt_negative_time) if self.adaptive_mcmc else {}
+            if pop is not None:
+                kw["keep_order"] = True  # set-aside walkers return to their own rows
             x, acceptance_rate_list = fn(x, energy_function, return_acceptance_rate=True, walker_offset=off, comm=comm,
                                          noise=mala_draws[0], uniforms=mala_draws[1], **kw)
-        return self._gather_final(x, comm, Bl), logweights, _host_counts(num_unique_idxs), sde_terms_all, acceptance_rate_list
+        return self._gather_final(x, comm, Bl, pop is not None), logweights, _host_counts(num_unique_idxs), sde_terms_all, acceptance_rate_list
 
-    def _gather_final(self, x, comm, Bl):
+    def _gather_final(self, x, comm, Bl, keep_order=False):
         """All-gather of the final shards.  After MALA every shard is [its valid walkers, its set-aside walkers]; the
         reference runs the chain on the gathered batch and therefore returns [all valid, all set-aside] (quirk Q7):
-        reorder to that when any rank set walkers aside."""
+        reorder to that when any rank set walkers aside.  ``keep_order`` (a run with ``populations``): the chain put the
+        set-aside walkers back in their places, row r stays in population r // S."""
         xg = comm.all_gather(x)
-        if comm.world == 1 or self.post_mcmc_steps <= 0:
+        if comm.world == 1 or self.post_mcmc_steps <= 0 or keep_order:
             return xg
         nv = comm.all_gather(torch.tensor([getattr(self, "_last_mala_valid", Bl)], device=x.device, dtype=torch.int64)).tolist()
         if min(nv) == Bl:
@@ -556,10 +699,12 @@ class WeightedSDEIntegrator:
         tail = [torch.arange(r * Bl + nv[r], (r + 1) * Bl) for r in range(comm.world)]
         return xg[torch.cat(head + tail).to(xg.device)]
 
-    def _resample_at_end(self, x, a, comm, times, energy_function, gamma_schedule, beta, u_iter, off, Bl):
+    def _resample_at_end(self, x, a, comm, times, energy_function, gamma_schedule, beta, u_iter, off, Bl, pop=None):
         """End-of-trajectory reweighting (sde_integration.py:158-183): a_next = log p_target(x) + gamma E_theta(h(t_end), x)
         (+ the running log-weights a), clamped at its 0.9 quantile, then global systematic resampling.
-        Returns (local slice of the resampled walkers, a_next over the global batch, number of distinct parents)."""
+        Returns (local slice of the resampled walkers, a_next over the global batch, number of distinct parents).  With
+        ``pop`` the clamp and the resampling are per population and rank-local; a_next is then this rank's and the number
+        of distinct parents is read from the run's log (row N)."""
         t_end = times[min(self.end_resampling_step, self.num_integration_steps - 1)]
         # every rank evaluates its own shard (the reference evaluates the gathered batch on every rank); only the
         # log-weights are gathered, the walkers move in the exchange
@@ -570,6 +715,12 @@ class WeightedSDEIntegrator:
         a_next = energy_function(x) + model_energy * _scalar(gamma_schedule.gamma(t_end))
         if a is not None:
             a_next = a_next + a
+        if pop is not None:
+            a_next = _lib.dev_tensor(a_next, "a_next").clone()
+            _lib.check(_lib.lib().pita_quantile_clamp(a_next.data_ptr(), a_next.shape[0], pop.S, 0.9,
+                                                      _lib.stream_ptr(a_next.device)), "pita_quantile_clamp")
+            x, _ = pop.event(x, a_next, 1.0, pop.N)
+            return x, a_next, None
         a_next = _quantile_clamp(comm.all_gather(a_next.contiguous()), 0.9)
         u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
         ids, _ = sample_cat_sys(a_next.shape[0], a_next, u)
@@ -631,16 +782,25 @@ class WeightedSDEIntegrator:
         return x
 
     def _mala(self, x, energy_function, adaptive, dt, noise=None, uniforms=None, return_acceptance_rate=False,
-              walker_offset=0, comm=None, fused=True):
+              walker_offset=0, comm=None, fused=True, keep_order=False):
         """MALA with the reference's finite-mask semantics (:362-470): non-finite-logp walkers are set aside and
         re-appended AFTER the valid ones (order not preserved, quirk Q7).  Proposal, accept/reject and the step-size
         adaptation run as HIP kernels with the step size on the device: no host synchronisation inside the chain (the
         acceptance rates are copied to the host afterwards, and only when the caller asks for them).
         With several ranks the acceptance count is all-reduced so the adaptation sees the global rate, as the
-        reference (which runs the chain on the gathered batch on every rank) does."""
+        reference (which runs the chain on the gathered batch on every rank) does.  ``keep_order`` (runs with
+        ``populations``): the set-aside walkers go back to their own rows instead."""
         n, d = self._geometry(x, energy_function)
         L = _lib.lib()
         x = _lib.dev_tensor(x, "x")
+
+        def join(x_valid, x_invalid):
+            if not keep_order:
+                return torch.cat([x_valid, x_invalid], dim=0)
+            out = x.clone()
+            out[valid] = x_valid
+            return out
+
         dev = x.device
         logp_all = energy_function(x)
         valid = torch.isfinite(logp_all)
@@ -683,7 +843,7 @@ class WeightedSDEIntegrator:
                 if energy_function.fused_mala(x_valid, logp, steps, dt_dev, adaptive, total, noise=nz, uniforms=uu, seed=key,
                                               walker_offset=walker_offset, walker_ids=ids, step0=0, remove_mean=rm,
                                               rates_out=rates) is not None:
-                    out = torch.cat([x_valid, x_invalid], dim=0)
+                    out = join(x_valid, x_invalid)
                     return (out, rates[:steps].tolist()) if return_acceptance_rate else (out, None)
             for i in range(steps):
                 if Bv > 0:
@@ -708,15 +868,15 @@ class WeightedSDEIntegrator:
                 _lib.check(L.pita_mala_adapt(dt_dev.data_ptr(), count.data_ptr(), total, int(adaptive),
                                              rates[i:].data_ptr(), st), "pita_mala_adapt")
                 done += 1
-        out = torch.cat([x_valid, x_invalid], dim=0)
+        out = join(x_valid, x_invalid)
         return (out, rates[:done].tolist()) if return_acceptance_rate else (out, None)
 
     def metropolis_hastings_mala(self, x, energy_function, return_acceptance_rate=False, noise=None, uniforms=None,
-                                 walker_offset=0, comm=None, fused=True):
+                                 walker_offset=0, comm=None, fused=True, keep_order=False):
         return self._mala(x, energy_function, False, float(self.dt_negative_time), noise, uniforms,
-                          return_acceptance_rate, walker_offset, comm, fused)
+                          return_acceptance_rate, walker_offset, comm, fused, keep_order)
 
     def metropolis_hastings_mala_adaptive(self, x, energy_function, dt_init, return_acceptance_rate=False, noise=None,
-                                          uniforms=None, walker_offset=0, comm=None, fused=True):
+                                          uniforms=None, walker_offset=0, comm=None, fused=True, keep_order=False):
         return self._mala(x, energy_function, True, float(dt_init), noise, uniforms, return_acceptance_rate,
-                          walker_offset, comm, fused)
+                          walker_offset, comm, fused, keep_order)

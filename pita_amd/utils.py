@@ -51,6 +51,54 @@ def sample_cat_sys_adaptive(bs, logits, theta, u=None, out=None):
     return ids, resampled, stats, n_unique
 
 
+MAX_POPULATION_SIZE = 2048  # walkers one block of pita_population_resample holds in LDS
+
+
+def sample_cat_sys_populations(logits, n_pop, theta, u=None, out=None):
+    """One resampling event for each of ``n_pop`` independent populations in ONE launch (pita_population_resample; an
+    extension).  ``logits`` [n_pop * S] holds the populations back to back, S <= 2 048; population p is decided and
+    resampled exactly as ``sample_cat_sys_adaptive(S, logits[p * S:(p + 1) * S], theta, u[p])`` would, bit for bit and
+    whatever ``n_pop`` and ``p`` are.  Returns ``(ids, resampled, stats, n_unique, logw_next)``, all device tensors and
+    none of them read by the host here: ``ids`` int64 [n_pop * S] are GLOBAL rows (p * S + parent), so ``gather_rows``
+    takes them as they are; ``resampled`` int32 [n_pop], ``stats`` float64 [n_pop, 6] and ``n_unique`` int64 [n_pop] are
+    the per-population outputs of ``sample_cat_sys_adaptive``; ``logw_next`` float32 [n_pop * S] is 0 where a population
+    resampled and ``logits`` where it did not.  ``theta >= 1`` is the fixed schedule.
+    ``u``: float64 [n_pop] uniforms in [0, 1), on the host or on the device (a device tensor is used as it is and not
+    checked); None draws ``torch.rand(n_pop, dtype=float64)`` from torch's CPU generator.  ``out``: optional
+    ``(resampled, stats, n_unique)`` to write into (rows of a caller's per-step buffers)."""
+    logits = _lib.dev_tensor(logits, "logits").reshape(-1)
+    n_pop = int(n_pop)
+    if n_pop < 1 or logits.shape[0] % n_pop != 0:
+        raise ValueError(f"{logits.shape[0]} log-weights do not split into {n_pop} populations")
+    S = logits.shape[0] // n_pop
+    dev = logits.device
+    if u is None:
+        u = torch.rand(n_pop, dtype=torch.float64)
+    if not isinstance(u, torch.Tensor):
+        u = torch.as_tensor(u, dtype=torch.float64)
+    if tuple(u.shape) != (n_pop,) or u.dtype != torch.float64:
+        raise ValueError(f"u must be a float64 tensor of shape ({n_pop},), got {u.dtype} {tuple(u.shape)}")
+    if not u.is_cuda:
+        if not bool(((u >= 0.0) & (u < 1.0)).all()):
+            raise ValueError("u must lie in [0, 1)")
+        u = u.to(dev)
+    u = u.contiguous()
+    ids = torch.empty(n_pop * S, device=dev, dtype=torch.int64)
+    logw_next = torch.empty(n_pop * S, device=dev, dtype=torch.float32)
+    if out is None:
+        out = (torch.empty(n_pop, device=dev, dtype=torch.int32), torch.empty(n_pop, 6, device=dev, dtype=torch.float64),
+               torch.empty(n_pop, device=dev, dtype=torch.int64))
+    resampled, stats, n_unique = out
+    L = _lib.lib()
+    nbytes = int(L.pita_population_resample_workspace_bytes(n_pop, S))
+    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)  # 8-byte aligned scratch
+    _lib.check(L.pita_population_resample(logits.data_ptr(), n_pop, S, u.data_ptr(), float(theta), ids.data_ptr(),
+                                          n_unique.data_ptr(), stats.data_ptr(), resampled.data_ptr(),
+                                          logw_next.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),
+               "pita_population_resample")
+    return ids, resampled, stats, n_unique, logw_next
+
+
 def rademacher_probes(B, n_particles, n_dim, n_probes, seed=0, walker_offset=0, step=0, device="cuda"):
     """[n_probes, B, n_particles * n_dim] Rademacher probes (+1 / -1) of the Hutchinson divergence estimator (the one
     the reference's utils.py ships beside ``compute_divergence_exact``) from the library's Philox stream
