@@ -715,6 +715,50 @@ int pita_population_resample(const float* logits, int64_t n_pop, int64_t pop_siz
                              int64_t* ids, int64_t* n_unique, double* stats, int* resampled, float* logw_next,
                              void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- weighted per-population observables
+ * An extension: the reference's evaluation counts every walker once and treats the batch as one population.
+ *
+ * The batch is n_pop populations of pop_size walkers, population p in rows [p * pop_size, (p + 1) * pop_size) (the
+ * integrator's layout).  logw: device float [n_pop * pop_size], nullable = unit weights.  Per population p:
+ *  m_p = max over the finite entries of its logw (0 when there is none; pita_logweight_stats' convention),
+ *  relative weight of walker i: w_i = exp((double)logw_i - m_p), in double;
+ *  a walker whose logw is NaN or +inf is left out of every sum and counted in n_bad, one whose logw is -inf has
+ *  weight 0 and is counted in n_neg_inf (and in `counts`).
+ * The weighted bin sums are FIXED-POINT integers: with shift = min(40, 62 - ceil(log2(pop_size * values per walker)))
+ * every value adds q_i = (uint64) rint(w_i * 2^shift) to its bin with integer adds only (LDS-privatised bins per block,
+ * a block works on one population, one 64-bit integer add per non-empty bin and block), so a population's total stays
+ * below 2^63 and its output bits depend neither on n_pop, nor on p, nor on the ORDER of the walkers inside the
+ * population, nor on the run.  shift < 20 (more than 2^42 values per population) is PITA_EUNSUPPORTED.  All argument
+ * checks run before any device call.  Outputs are overwritten.
+ *
+ * pita_weighted_histogram: v float [n_pop * pop_size * per_walker], value k belongs to walker k / per_walker; bins as
+ * pita_histogram counts them (the same device function), 1 <= nbins <= 1024.
+ *  wsum   uint64 [n_pop, nbins]  the fixed-point sums; the weighted histogram is wsum * 2^-shift
+ *  counts uint64 [n_pop, nbins]  the plain counts over the walkers that were not left out; with n_pop = 1,
+ *                                per_walker = 1 and logw = NULL exactly what pita_histogram writes
+ *  info   double [n_pop, 4]      {m_p, n_bad, n_neg_inf, shift} */
+int pita_weighted_histogram(const float* v, const float* logw /*nullable*/, int64_t n_pop, int64_t pop_size,
+                            int64_t per_walker, const float* edges, int nbins, unsigned long long* wsum,
+                            unsigned long long* counts, double* info, void* stream);
+/* The same histogram over the n (n - 1) / 2 upper-triangle pair distances of every walker, from the coordinates x
+ * (float [n_pop * pop_size, n_particles * n_dim]) with no distance array in memory: a block stages a chunk of its
+ * population's walkers in LDS and its threads stride over the (walker, pair) items; every pair carries its walker's
+ * weight.  2 <= n_particles <= 256, 1 <= n_dim <= 3.  Arithmetic, in fp32 without contraction, so that a numpy float32
+ * restatement is bit-identical: per dimension delta = x_j - x_i (i < j); s = delta_0 * delta_0, then s = s + delta_1 *
+ * delta_1, then s = s + delta_2 * delta_2; r = sqrt(s) correctly rounded.  wsum, counts and info are bit for bit those
+ * of pita_weighted_histogram(per_walker = n (n - 1) / 2) on these distances. */
+int pita_pair_distance_histogram(const float* x, const float* logw /*nullable*/, int64_t n_pop, int64_t pop_size,
+                                 int n_particles, int n_dim, const float* edges, int nbins, unsigned long long* wsum,
+                                 unsigned long long* counts, double* info, void* stream);
+/* Weighted moments of one value per walker: out double [n_pop, 6] = {m_p, sum w, sum w v, sum w v^2, n_bad, n_neg_inf}
+ * (v float [n_pop * pop_size]).  Here a walker is ALSO left out, and counted in n_bad, when its value is not finite;
+ * n_neg_inf counts the walkers with logw = -inf among the others; m_p is over all finite logw of the population.
+ * fp64 sums in a fixed order: one block of 1 024 threads per population, thread t takes rows t, t + 1024, ...,
+ * xor-shuffle wave reduction, the 16 wave partials added in index order (pita_logweight_stats' order).  The bits of a
+ * population therefore depend on the ORDER of its rows (unlike the two histograms), but neither on n_pop nor on p. */
+int pita_weighted_moments(const float* v, const float* logw /*nullable*/, int64_t n_pop, int64_t pop_size, double* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

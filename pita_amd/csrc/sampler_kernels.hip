@@ -10,6 +10,7 @@
 //   models/components/sde_integration.py:28-45     mala_proposal
 //   models/components/sde_integration.py:379-398, 430-461   MALA accept/reject, step-size adaptation
 #include "common.h"
+#include "hist_common.h"
 
 namespace pita {
 
@@ -756,8 +757,7 @@ extern "C" int pita_moments4(const float* v0, const float* v1, const float* v2, 
 // values outside [edges[0], edges[nbins]] and NaNs not counted.  One pass over the sample: bins privatised in LDS per
 // block (one copy per wave: the four waves of a block do not contend), a guessed bin from the uniform spacing corrected
 // against the edges (numpy's own rule, so that counts agree with numpy.histogram bin for bin), one 64-bit add per bin
-// and block at the end.
-constexpr int HIST_MAX_BINS = 1024;
+// and block at the end.  The bin rule is hist_bin (hist_common.h), shared with the weighted histograms.
 __global__ void __launch_bounds__(256) histogram_kernel(const float* __restrict__ v, long long n, const float* __restrict__ edges,
                                                         int nbins, unsigned long long* __restrict__ counts) {
   extern __shared__ unsigned hist_lds[];  // [4 waves][nbins] counters, then [nbins + 1] edges
@@ -769,13 +769,8 @@ __global__ void __launch_bounds__(256) histogram_kernel(const float* __restrict_
   const float lo = e[0], hi = e[nbins];
   const float inv = (float)nbins / (hi - lo);
   for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long long)gridDim.x * 256) {
-    const float x = v[k];
-    if (!(x >= lo && x <= hi)) continue;  // out of range or NaN
-    int i = (int)((x - lo) * inv);
-    i = i < 0 ? 0 : (i > nbins - 1 ? nbins - 1 : i);
-    while (i > 0 && x < e[i]) --i;
-    while (i < nbins - 1 && x >= e[i + 1]) ++i;
-    atomicAdd(&bins[i], 1u);
+    const int i = hist_bin(v[k], e, nbins, lo, hi, inv);
+    if (i >= 0) atomicAdd(&bins[i], 1u);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nbins; i += 256) {

@@ -21,21 +21,66 @@ def _w_1d(a: torch.Tensor, b: torch.Tensor, p: int):
     return float(((a - b).abs() ** p).mean())
 
 
-def energy_distances(pred: torch.Tensor, true: torch.Tensor, prefix: str = "", energy_threshold: float = 1000):
+def _relative_weights(logw: torch.Tensor) -> torch.Tensor:
+    """exp(logw - max over the finite entries) in double; NaN and +inf entries get weight 0 (left out), -inf gives 0."""
+    lw = logw.double().flatten()
+    fin = torch.isfinite(lw)
+    m = lw[fin].max() if bool(fin.any()) else lw.new_zeros(())
+    return torch.where(fin, torch.exp(lw - m), torch.zeros_like(lw))
+
+
+def _w_1d_weighted(a: torch.Tensor, wa, b: torch.Tensor, wb, p: int):
+    """1-D optimal-transport cost sum |Qa - Qb|^p dq between two WEIGHTED empirical measures (weights ``wa`` / ``wb``
+    >= 0 of the shape of ``a`` / ``b``, None = equal weights): the two quantile functions are merged on the union of
+    their cumulative-weight grids and compared at the midpoint of every interval.  fp64, torch ops on the inputs' device."""
+    def grid(v, w):
+        v, order = torch.sort(v.double().flatten())
+        w = torch.ones_like(v) if w is None else w.double().flatten()[order]
+        c = torch.cumsum(w, 0)
+        return v, c / c[-1]
+
+    a, ca = grid(a, wa)
+    b, cb = grid(b, wb)
+    q, _ = torch.sort(torch.cat([ca, cb]))
+    dq = torch.diff(torch.cat([q.new_zeros(1), q]))
+    mid = q - 0.5 * dq  # an interval of zero width contributes nothing, wherever its midpoint lands
+    ia = torch.clamp(torch.searchsorted(ca, mid), max=a.numel() - 1)
+    ib = torch.clamp(torch.searchsorted(cb, mid), max=b.numel() - 1)
+    return float((dq * (a[ia] - b[ib]).abs() ** p).sum())
+
+
+def energy_distances(pred: torch.Tensor, true: torch.Tensor, prefix: str = "", energy_threshold: float = 1000,
+                     pred_logweights: torch.Tensor = None):
     """Same dictionary as the reference's ``energy_distances`` (W2 = sqrt of the squared-euclidean 1-D OT cost,
-    W1 = euclidean cost, plus the 'cropped' variants that zero out |E| > threshold entries of ``pred``)."""
-    out = {f"{prefix}/energy_w2": math.sqrt(_w_1d(true, pred, 2)), f"{prefix}/energy_w1": _w_1d(true, pred, 1),
-           f"{prefix}/mean_dist": float((pred.double().mean() - true.double().mean()).abs())}
+    W1 = euclidean cost, plus the 'cropped' variants that zero out |E| > threshold entries of ``pred``).
+    ``pred_logweights`` (an extension, shape of ``pred``): importance log-weights of the generated energies; the
+    distances, ``mean_dist`` and the cropped variants then use the self-normalised weights (``_w_1d_weighted``)."""
     mask = (pred < -energy_threshold) | (pred > energy_threshold)
     cp, ct = (~mask) * pred, (~mask) * true if mask.shape == true.shape else true
+    if pred_logweights is not None:
+        w = _relative_weights(pred_logweights)
+        mean = (w * pred.double().flatten()).sum() / w.sum()
+        return {f"{prefix}/energy_w2": math.sqrt(_w_1d_weighted(true, None, pred, w, 2)),
+                f"{prefix}/energy_w1": _w_1d_weighted(true, None, pred, w, 1),
+                f"{prefix}/mean_dist": float((mean - true.double().mean()).abs()),
+                f"{prefix}/cropped_energy_w2": math.sqrt(_w_1d_weighted(ct, None, cp, w, 2)),
+                f"{prefix}/cropped_energy_w1": _w_1d_weighted(ct, None, cp, w, 1),
+                f"{prefix}/num_cropped": int(mask.sum())}
+    out = {f"{prefix}/energy_w2": math.sqrt(_w_1d(true, pred, 2)), f"{prefix}/energy_w1": _w_1d(true, pred, 1),
+           f"{prefix}/mean_dist": float((pred.double().mean() - true.double().mean()).abs())}
     out[f"{prefix}/cropped_energy_w2"] = math.sqrt(_w_1d(ct, cp, 2))
     out[f"{prefix}/cropped_energy_w1"] = _w_1d(ct, cp, 1)
     out[f"{prefix}/num_cropped"] = int(mask.sum())
     return out
 
 
-def interatomic_w2(energy_function, pred: torch.Tensor, true: torch.Tensor) -> float:
-    """W2 between the pooled interatomic-distance samples of two walker sets."""
+def interatomic_w2(energy_function, pred: torch.Tensor, true: torch.Tensor, pred_logweights: torch.Tensor = None) -> float:
+    """W2 between the pooled interatomic-distance samples of two walker sets; with ``pred_logweights`` (one per walker
+    of ``pred``) every distance of a generated walker carries that walker's weight."""
+    if pred_logweights is not None:
+        d_pred = energy_function.interatomic_dist(pred)
+        w = _relative_weights(pred_logweights).repeat_interleave(d_pred.shape[-1])
+        return math.sqrt(_w_1d_weighted(energy_function.interatomic_dist(true), None, d_pred, w, 2))
     return math.sqrt(_w_1d(energy_function.interatomic_dist(true), energy_function.interatomic_dist(pred), 2))
 
 
@@ -88,8 +133,133 @@ def _density(counts: torch.Tensor, edges):
     return n / db / n.sum()
 
 
+class WeightedHistogram:
+    """Result of ``weighted_histogram`` / ``pair_distance_histogram`` for P populations:
+
+    * ``raw``     int64 [P, nbins] on the device: the kernel's fixed-point bin sums (below 2^63), bitwise independent of
+      the order of the walkers inside a population, of P and of the population's place in the batch;
+    * ``counts``  int64 [P, nbins] on the device: plain counts over the walkers that were not left out;
+    * ``weights`` float64 [P, nbins] on the device: ``raw * 2^-shift``, sums of the relative weights exp(logw - log_scale);
+    * ``log_scale``, ``n_bad``, ``n_neg_inf`` float64 numpy [P]: the maximum finite log-weight of each population (0 where
+      there is none), its NaN / +inf entries (left out) and its -inf entries (weight 0);  ``shift`` the fixed-point shift."""
+
+    def __init__(self, raw, counts, info):
+        h = info.cpu().numpy()
+        self.raw, self.counts = raw, counts
+        self.log_scale, self.n_bad, self.n_neg_inf, self.shift = h[:, 0].copy(), h[:, 1].copy(), h[:, 2].copy(), int(h[0, 3])
+        self.weights = raw.double() * 2.0 ** -self.shift
+
+    def density(self, edges):
+        """Self-normalised density per population, numpy float64 [P, nbins] (``numpy.histogram(density=True, weights=w)``
+        row by row); a row is NaN where the population's weight sum is 0."""
+        import numpy as np
+
+        w = self.weights.cpu().numpy()
+        db = np.array(np.diff(np.asarray(edges)), float)
+        tot = w.sum(axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tot > 0, w / db / tot, np.nan)
+
+
+def _population_args(n_rows: int, logweights, populations, device):
+    P = 1 if populations is None else int(populations)
+    if P < 1 or n_rows < 1 or n_rows % P:
+        raise ValueError(f"{n_rows} walkers do not split into populations={populations} equal populations")
+    lw = None
+    if logweights is not None:
+        from . import _lib
+
+        lw = _lib.dev_tensor(logweights.reshape(-1), "logweights")
+        if lw.numel() != n_rows or lw.device != device:
+            raise ValueError(f"logweights: expected {n_rows} entries on {device}, got {lw.numel()} on {lw.device}")
+    return P, n_rows // P, lw
+
+
+def weighted_histogram(values: torch.Tensor, edges, logweights: torch.Tensor = None, populations: int = 1,
+                       per_walker: int = 1) -> WeightedHistogram:
+    """Importance-weighted histogram per population (pita_weighted_histogram; an extension).  ``values``: device tensor of
+    ``B * per_walker`` entries, value k belonging to walker ``k // per_walker``; the B walkers are ``populations`` equal
+    slices in the integrator's layout; ``logweights`` [B] (None = unit weights); ``edges`` and the bin rule as in
+    ``histogram``.  Order-independent fixed-point sums, see ``WeightedHistogram``."""
+    from . import _lib
+
+    v = _lib.dev_tensor(values.reshape(-1).float().contiguous(), "values")
+    if per_walker < 1 or v.numel() % per_walker:
+        raise ValueError(f"{v.numel()} values are not {per_walker} per walker")
+    P, S, lw = _population_args(v.numel() // per_walker, logweights, populations, v.device)
+    e = torch.as_tensor(edges, dtype=torch.float32).to(v.device).contiguous()
+    nb = e.numel() - 1
+    raw, counts = (torch.empty(P, max(nb, 0), dtype=torch.int64, device=v.device) for _ in range(2))
+    info = torch.empty(P, 4, dtype=torch.float64, device=v.device)
+    _lib.check(_lib.lib().pita_weighted_histogram(v.data_ptr(), _lib.ptr(lw), P, S, per_walker, e.data_ptr(), nb, raw.data_ptr(),
+                                                  counts.data_ptr(), info.data_ptr(), _lib.stream_ptr(v.device)),
+               "pita_weighted_histogram")
+    return WeightedHistogram(raw, counts, info)
+
+
+def pair_distance_histogram(energy_function, samples: torch.Tensor, edges, logweights: torch.Tensor = None,
+                            populations: int = 1) -> WeightedHistogram:
+    """The same histogram over the interatomic distances of ``samples`` [B, n * d] (unnormalised as
+    ``energy_function.interatomic_dist`` does), computed from the coordinates in one call
+    (pita_pair_distance_histogram): the [B, n (n - 1) / 2] distance array is never written."""
+    from . import _lib
+
+    n, d = energy_function.n_particles, energy_function.n_spatial_dim
+    x = samples.reshape(-1, n * d)
+    if energy_function.should_normalize:
+        x = energy_function.unnormalize(x)
+    x = _lib.dev_tensor(x, "samples")
+    P, S, lw = _population_args(x.shape[0], logweights, populations, x.device)
+    e = torch.as_tensor(edges, dtype=torch.float32).to(x.device).contiguous()
+    nb = e.numel() - 1
+    raw, counts = (torch.empty(P, max(nb, 0), dtype=torch.int64, device=x.device) for _ in range(2))
+    info = torch.empty(P, 4, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().pita_pair_distance_histogram(x.data_ptr(), _lib.ptr(lw), P, S, n, d, e.data_ptr(), nb, raw.data_ptr(),
+                                                       counts.data_ptr(), info.data_ptr(), _lib.stream_ptr(x.device)),
+               "pita_pair_distance_histogram")
+    return WeightedHistogram(raw, counts, info)
+
+
+def weighted_mean(values: torch.Tensor, logweights: torch.Tensor = None, populations: int = 1):
+    """Self-normalised importance estimate of one value per walker, per population (pita_weighted_moments; fp64 sums in a
+    fixed order): a dict of float64 numpy arrays [P] -- ``mean`` = sum w v / sum w, ``var`` = sum w v^2 / sum w - mean^2
+    (weighted, biased), ``ess`` and ``ess_fraction`` = ess / pop_size of the population's log-weights (``logweight_stats``
+    on its slice; the number of kept walkers without log-weights), ``n_bad`` the walkers left out (log-weight NaN or +inf,
+    or a value that is not finite), ``n_neg_inf`` and ``log_scale``.  ``mean`` and ``var`` are NaN where sum w is 0."""
+    import numpy as np
+    from . import _lib
+
+    v = _lib.dev_tensor(values.reshape(-1), "values")
+    P, S, lw = _population_args(v.numel(), logweights, populations, v.device)
+    out = torch.empty(P, 6, dtype=torch.float64, device=v.device)
+    _lib.check(_lib.lib().pita_weighted_moments(v.data_ptr(), _lib.ptr(lw), P, S, out.data_ptr(), _lib.stream_ptr(v.device)),
+               "pita_weighted_moments")
+    h = out.cpu().numpy()
+    s0, s1, s2 = h[:, 1], h[:, 2], h[:, 3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(s0 > 0, s1 / s0, np.nan)
+        var = np.where(s0 > 0, s2 / s0 - mean * mean, np.nan)
+    ess = s0.copy() if lw is None else np.atleast_1d(logweight_stats(lw.reshape(P, S))["ess"])
+    return {"mean": mean, "var": var, "ess": ess, "ess_fraction": ess / S, "n_bad": h[:, 4].copy(),
+            "n_neg_inf": h[:, 5].copy(), "log_scale": h[:, 0].copy()}
+
+
+def population_summary(per_pop):
+    """Error bar over independent populations: ``per_pop`` is [P] or [P, ...], one estimate per population.  Returns a
+    dict with ``mean`` = the plain mean over the populations whose estimate is finite (every entry of the row),
+    ``stderr`` = std(ddof=1) / sqrt(n_used) over the same rows (NaN for n_used < 2) and ``n_used``."""
+    import numpy as np
+
+    a = np.asarray(per_pop, dtype=np.float64)
+    used = a[np.isfinite(a.reshape(a.shape[0], -1)).all(axis=1)]
+    n = used.shape[0]
+    nan = np.full(a.shape[1:], np.nan)
+    return {"mean": used.mean(axis=0) if n >= 1 else nan,
+            "stderr": used.std(axis=0, ddof=1) / math.sqrt(n) if n >= 2 else nan, "n_used": n}
+
+
 def sample_histograms(energy_function, samples: torch.Tensor, test_set: torch.Tensor, energy_samples: torch.Tensor = None,
-                      bins: int = 100):
+                      bins: int = 100, logweights: torch.Tensor = None, populations: int = None):
     """The numbers under the reference's sample figure (``get_dataset_fig``, base_molecule_energy_function.py:160-254):
     two pairs of ``bins``-bin density arrays, generated samples against the test set --
 
@@ -98,17 +268,33 @@ def sample_histograms(energy_function, samples: torch.Tensor, test_set: torch.Te
     * energies ``-log p``: ``bins`` equal bins over ``(min(E_test) - 10, max(E_test) + 10)`` (:213-238).
 
     Bin edges are numpy's own for that range and dtype (``numpy.histogram_bin_edges``), the counting runs on the device.
-    Returns a dict of numpy arrays: ``dist_edges, dist_test, dist_samples, energy_edges, energy_test, energy_samples``."""
+    Returns a dict of numpy arrays: ``dist_edges, dist_test, dist_samples, energy_edges, energy_test, energy_samples``.
+
+    An extension, off unless asked for: with ``logweights`` ([B] importance log-weights of ``samples``) and / or
+    ``populations`` (P equal slices of the walkers, the integrator's layout) the generated side is weighted and taken per
+    population -- ``dist_samples_pop`` / ``energy_samples_pop`` [P, bins] are the self-normalised weighted densities of the
+    populations (the distances by the fused pair-distance kernel), ``dist_samples`` / ``energy_samples`` their
+    ``population_summary`` mean and ``dist_samples_stderr`` / ``energy_samples_stderr`` its standard error.  The test-set
+    side is unweighted as before."""
     import numpy as np
 
     d_test = energy_function.interatomic_dist(test_set).reshape(-1).float()
-    d_gen = energy_function.interatomic_dist(samples).reshape(-1).float()
     mm = torch.stack([d_test.min(), d_test.max()]).cpu().numpy().astype(np.float32)
     d_edges = np.histogram_bin_edges(mm, bins=bins)
     e_test = -energy_function(test_set).float()
     e_gen = -(energy_function(samples) if energy_samples is None else energy_samples).float()
     em = torch.stack([e_test.min(), e_test.max()]).cpu().numpy().astype(np.float32)
     e_edges = np.histogram_bin_edges(em, bins=bins, range=(float(em[0]) - 10, float(em[1]) + 10))
+    if logweights is not None or populations is not None:
+        P = 1 if populations is None else populations
+        d_pop = pair_distance_histogram(energy_function, samples, d_edges, logweights, P).density(d_edges)
+        e_pop = weighted_histogram(e_gen, e_edges, logweights, P).density(e_edges)
+        d_sum, e_sum = population_summary(d_pop), population_summary(e_pop)
+        return {"dist_edges": d_edges, "dist_test": _density(histogram(d_test, d_edges), d_edges),
+                "dist_samples": d_sum["mean"], "dist_samples_pop": d_pop, "dist_samples_stderr": d_sum["stderr"],
+                "energy_edges": e_edges, "energy_test": _density(histogram(e_test, e_edges), e_edges),
+                "energy_samples": e_sum["mean"], "energy_samples_pop": e_pop, "energy_samples_stderr": e_sum["stderr"]}
+    d_gen = energy_function.interatomic_dist(samples).reshape(-1).float()
     return {"dist_edges": d_edges, "dist_test": _density(histogram(d_test, d_edges), d_edges),
             "dist_samples": _density(histogram(d_gen, d_edges), d_edges),
             "energy_edges": e_edges, "energy_test": _density(histogram(e_test, e_edges), e_edges),
