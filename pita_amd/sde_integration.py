@@ -23,7 +23,15 @@ How the work is laid out on MI355X (differences from the reference are deliberat
 sum of squares, count over the global batch, reduced on the device) that answers ``.mean()`` / ``.std()`` -- the only
 things the reference's callers ever ask of these tensors (energytemp_module.py:938-945,1132-1143);
 ``record_terms=True`` materialises the full per-step tensors instead (per-step launch path).
+
+Layout: ``integrate_sde`` puts what is fixed for a run into one ``_Run`` record and runs the regime's loop -- its own for
+the default regime (log-weights identically zero, fused launches between events), ``_integrate_debiased`` per step for the
+Feynman-Kac weights --, then ``_finish_weights`` (end-of-run reweighting, diagnostics, counts) and ``_post_process``
+(descent, MALA, final all-gather).  Who resamples, and with which collectives, is one policy object per run, chosen once
+from ``(populations, ess_threshold)``: ``_GlobalEvents`` (fixed schedule, or ESS-triggered with a threshold) or
+``_PopulationEvents``; both answer ``skip_zero_weight_events``, ``event``, ``end_event``, ``collect``, ``gather``, ``finish``.
 """
+import collections
 import math
 
 import numpy as np
@@ -40,11 +48,11 @@ def _scalar(v):
     return float(v.reshape(-1)[0]) if isinstance(v, torch.Tensor) else float(v)
 
 
-def _quantile_clamp(a, q):
-    """clamp(a, max=quantile(a, q)) over the whole vector through the K11 kernel (sde_integration.py:179)."""
+def _quantile_clamp(a, q, chunk=None):
+    """clamp(a, max=quantile(a, q)) on a copy (K11 kernel; sde_integration.py:179): whole vector, or per ``chunk`` entries."""
     a = _lib.dev_tensor(a, "a").clone()
-    _lib.check(_lib.lib().pita_quantile_clamp(a.data_ptr(), a.shape[0], a.shape[0], float(q), _lib.stream_ptr(a.device)),
-               "pita_quantile_clamp")
+    _lib.check(_lib.lib().pita_quantile_clamp(a.data_ptr(), a.shape[0], a.shape[0] if chunk is None else chunk, float(q),
+                                              _lib.stream_ptr(a.device)), "pita_quantile_clamp")
     return a
 
 
@@ -148,18 +156,10 @@ class _Comm:
         generator, utils.py:111-120, and relies on identically seeded ranks; the exchange below needs agreement)."""
         if u is None:
             u = torch.rand(size=(1,), dtype=torch.float64)
-        u = torch.as_tensor(u, dtype=torch.float64).reshape(-1)[:1].clone()
-        if self.world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
-            if torch.distributed.get_backend() == "nccl":
-                ud = u.cuda()
-                torch.distributed.broadcast(ud, 0)
-                u = ud.cpu()
-            else:
-                torch.distributed.broadcast(u, 0)
-        return u
+        return self.broadcast_host(torch.as_tensor(u, dtype=torch.float64).reshape(-1)[:1].clone())
 
     def broadcast_host(self, t):
-        """Rank 0's host tensor ``t`` on every rank (the uniforms of a run with ``populations``: once, before the loop)."""
+        """Rank 0's host tensor ``t`` on every rank: an event's uniform, or all those of a run with ``populations`` at once."""
         if self.world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
             if torch.distributed.get_backend() == "nccl":
                 td = t.cuda()
@@ -236,30 +236,6 @@ def _host_counts(counts):
     return counts
 
 
-class _EventLog:
-    """Per-step outputs of the adaptive resampling events of one run (``ess_threshold``), preallocated on the device:
-    the kernel of step s writes row s, the host reads everything once after the loop (``finish``).  With ``P`` (a run
-    with ``populations``) every row has one column per population of ``B`` walkers."""
-
-    def __init__(self, N, B, device, P=None):
-        cols = () if P is None else (P,)
-        self.stats = torch.full((N,) + cols + (6,), float("nan"), dtype=torch.float64, device=device)
-        self.flags = torch.zeros((N,) + cols, dtype=torch.int32, device=device)
-        self.counts = torch.full((N,) + cols, B, dtype=torch.int64, device=device)
-
-    def row(self, step):
-        return self.flags[step], self.stats[step], self.counts[step]
-
-    def finish(self, final_logweights):
-        """``last_weight_stats``; ``final_logweights``: the last row of the run's log-weights (device)."""
-        h = self.stats.cpu().numpy()
-        resampled = self.flags.cpu().numpy() != 0
-        lmw = h[:, 1].copy()
-        tail = logweight_stats(final_logweights)["log_mean_weight"]
-        return {"ess": h[:, 2].copy(), "ess_fraction": h[:, 3].copy(), "log_mean_weight": lmw, "resampled": resampled,
-                "log_z": float(lmw[resampled].sum()) + tail}
-
-
 def population_layout(Bg, world, populations, batch_size):
     """``(S, populations per rank, clamp chunk)`` of a run of ``Bg`` walkers in ``populations`` independent populations
     over ``world`` ranks: S = Bg / populations walkers each, whole populations per rank, and the 0.9-quantile clamp of the
@@ -282,14 +258,119 @@ def population_layout(Bg, world, populations, batch_size):
     return S, P // world, chunk
 
 
-class _PopulationRun:
-    """One run with ``populations=P``: the layout, this rank's columns of the run's uniforms [events, P] on the device
-    (drawn or taken once, rank 0's on every rank) and the event log, one row per step and one more for
-    ``resample_at_end``.  Every event is rank-local: one pita_population_resample launch and the row gather."""
+class _Events:
+    """What the two resampling policies of a run share: the log of its events, preallocated on the device with one
+    column per population -- the kernel of step s writes row s, the host reads everything once after the loop -- and the
+    diagnostics made of it.  ``P`` populations of ``S`` walkers; ``theta``: the ESS threshold, None for the fixed
+    schedule; ``zero_a`` (debiased regime): the shard's zero log-weights, never written to."""
 
-    def __init__(self, comm, Bg, P, batch_size, N, n_events, resample_u, device):
-        self.P, self.N = P, N
-        self.S, self.Pl, self.chunk = population_layout(Bg, comm.world, P, batch_size)
+    keep_order = False  # after MALA the set-aside walkers go behind the valid ones (quirk Q7)
+    synthetic = ()  # due steps settled on the host because the weights are identically zero: ESS = S, mean weight 1
+
+    def _alloc_log(self, rows, cols, device):
+        self.stats = torch.full((rows, cols, 6), float("nan"), dtype=torch.float64, device=device)
+        self.flags = torch.zeros((rows, cols), dtype=torch.int32, device=device)
+        self.counts = torch.full((rows, cols), self.S, dtype=torch.int64, device=device)
+
+    def row(self, step):
+        return self.flags[step], self.stats[step], self.counts[step]
+
+    def collect(self, a):  # the row of the run's log-weights that a step's `a` makes
+        return a
+
+    def gather(self, rows):  # collected rows -> rows over the global batch
+        return rows
+
+    def _weight_stats(self, st, resampled, final_logweights):
+        """Per-event arrays [N, P] and ``log_z`` [P] from the log's host copy (``st`` [N, P, 6], ``resampled`` [N, P]) and
+        the last row of the run's log-weights (device)."""
+        for s in self.synthetic:
+            st[s, :, 1], st[s, :, 2], st[s, :, 3] = 0.0, float(self.S), 1.0
+            resampled[s] = self.theta >= 1.0
+        tail = logweight_stats(final_logweights.reshape(self.P, -1))["log_mean_weight"]
+        lmw = st[:, :, 1]
+        log_z = np.array([lmw[resampled[:, p], p].sum() for p in range(self.P)], np.float64) + tail
+        return {"ess": st[:, :, 2].copy(), "ess_fraction": st[:, :, 3].copy(), "log_mean_weight": lmw.copy(),
+                "resampled": resampled, "log_z": log_z}
+
+
+class _GlobalEvents(_Events):
+    """One population over all ranks, like the reference's: an event all-gathers the log-weights, every rank resamples
+    them alike with rank 0's uniform, the walkers move in ``_Comm.exchange_rows``.  With a threshold the event is decided
+    on the device (no host read) and its uniform is drawn whether or not it resamples (the fixed schedule's stream)."""
+
+    def __init__(self, comm, Bg, Bl, N, theta, resample_u, device, weighted, clamp_chunk):
+        self.comm, self.Bg, self.Bl, self.N, self.theta, self.clamp_chunk = comm, Bg, Bl, N, theta, clamp_chunk
+        self.P, self.S = 1, comm.world * Bl
+        self.u_iter = iter(resample_u) if resample_u is not None else None
+        self.n_unique = {}  # step -> distinct parents of its event, 0-dim device tensors (row N: the end-of-run event)
+        self.zero_a = torch.zeros(Bl, device=device) if weighted else None
+        self.stats = None  # zero weights have no log: their diagnostics are known on the host
+        if weighted and theta is not None:
+            self._alloc_log(N, 1, device)
+
+    def _uniform(self):
+        return self.comm.shared_uniform(next(self.u_iter) if self.u_iter is not None else None)
+
+    def skip_zero_weight_events(self, due):
+        """The due events that still run on the device when the log-weights are identically zero: ESS = batch, so below
+        a threshold of 1 none resamples -- no kernel, but the uniforms are drawn as the fixed schedule would draw them."""
+        if self.theta is not None:
+            self.synthetic = due
+            if self.theta < 1.0:
+                for _ in due:
+                    self._uniform()
+                return []
+        return due
+
+    def event(self, x, a, step):
+        """``(x, a)`` after the event of ``step``; ``a`` None: log-weights identically zero (nothing to gather)."""
+        ag = torch.zeros(self.S, device=x.device) if a is None else self.comm.all_gather(a)
+        u = self._uniform()
+        if self.stats is None:
+            ids, _ = sample_cat_sys(ag.shape[0], ag, u)
+            self.n_unique[step] = _count_distinct(ids)
+            return self.comm.exchange_rows(x, ids, self.Bl), self.zero_a
+        ids, resampled, _, self.n_unique[step] = sample_cat_sys_adaptive(ag.shape[0], ag, self.theta, u,
+                                                                         out=tuple(t[0] for t in self.row(step)))
+        x = self.comm.exchange_rows(x, ids, self.Bl)  # identity ids move nothing
+        return x, torch.where(resampled != 0, self.zero_a, a)
+
+    def end_event(self, x, a_next):
+        """Always resamples, on ``a_next`` clamped at the 0.9 quantile of the gathered vector: ``(x, global a_next)``."""
+        a_next = _quantile_clamp(self.comm.all_gather(a_next.contiguous()), 0.9)
+        ids, _ = sample_cat_sys(a_next.shape[0], a_next, self._uniform())
+        x = self.comm.exchange_rows(x, ids, self.Bl)
+        self.n_unique[self.N] = _count_distinct(ids)
+        return x, a_next
+
+    def collect(self, a):
+        return self.comm.all_gather(a)  # at every step
+
+    def finish(self, final_logweights, n_rows):
+        """``(last_weight_stats, counts)``: None under the fixed schedule, per-event arrays [N] otherwise; the counts of
+        rows without an event are the batch, the others still device scalars (``_host_counts`` reads them at once)."""
+        counts = [self.n_unique.get(s, self.Bg) for s in range(n_rows)]
+        if self.theta is None:
+            return None, counts
+        if self.stats is None:
+            st, resampled = np.full((self.N, 1, 6), np.nan), np.zeros((self.N, 1), dtype=bool)
+        else:
+            st, resampled = self.stats.cpu().numpy(), self.flags.cpu().numpy() != 0
+        stats = self._weight_stats(st, resampled, final_logweights)
+        return {k: float(v[0]) if k == "log_z" else v[:, 0] for k, v in stats.items()}, counts
+
+
+class _PopulationEvents(_Events):
+    """``populations=P``: the layout, this rank's columns of the run's uniforms [events, P] on the device (drawn or taken
+    once, rank 0's on every rank) and the log, with one more row for ``resample_at_end``.  Every event is rank-local: one
+    pita_population_resample launch and the row gather; log-weights and log are gathered once, after the loop."""
+
+    keep_order = True  # set-aside walkers return to their own rows: row r stays in population r // S
+
+    def __init__(self, comm, Bg, P, batch_size, N, n_events, theta, resample_u, device, weighted):
+        self.comm, self.P, self.N, self.theta = comm, P, N, theta
+        self.S, self.Pl, self.clamp_chunk = population_layout(Bg, comm.world, P, batch_size)
         if resample_u is None:
             u = torch.rand((n_events, P), dtype=torch.float64)
         else:
@@ -301,41 +382,58 @@ class _PopulationRun:
         u = comm.broadcast_host(u)
         lo = comm.rank * self.Pl
         self.u = u[:, lo:lo + self.Pl].contiguous().to(device)
-        self.log = _EventLog(N + 1, self.S, device, self.Pl)
+        self._alloc_log(N + 1, self.Pl, device)
         self.next_event = 0
+        self.zero_a = torch.zeros(self.Pl * self.S, device=device) if weighted else None
 
-    def event(self, x, a, theta, row):
-        """(x, a) after the event whose outputs go to row ``row`` of the log; ``a``: this rank's log-weights."""
+    def skip_zero_weight_events(self, due):
+        """As ``_GlobalEvents``'s; a run's uniforms are drawn up front, so skipping an event only moves the cursor."""
+        if self.theta is None or self.theta >= 1.0:
+            return due
+        self.synthetic = due
+        self.next_event += len(due)
+        return []
+
+    def _launch(self, x, a, theta, row):
         u = self.u[self.next_event]
         self.next_event += 1
-        ids, _, _, _, a_next = sample_cat_sys_populations(a, self.Pl, 1.0 if theta is None else theta, u,
-                                                          out=self.log.row(row))
+        ids, _, _, _, a_next = sample_cat_sys_populations(a, self.Pl, theta, u, out=self.row(row))
         return gather_rows(x, ids), a_next
 
-    def gather_rows_of_ranks(self, comm, t):
-        """[R, Bl, ...] of every rank -> [R, Bg, ...] in population order (one all-gather)."""
-        if comm.world == 1:
-            return t
-        g = comm.all_gather(t.contiguous()).reshape((comm.world,) + tuple(t.shape))
-        return g.transpose(0, 1).reshape((t.shape[0], comm.world * t.shape[1]) + tuple(t.shape[2:]))
+    def event(self, x, a, step):
+        """``(x, a)`` after the event of ``step`` on this rank's populations; ``a`` None: identically zero."""
+        if a is None:
+            a = torch.zeros(self.Pl * self.S, device=x.device)
+        return self._launch(x, a, 1.0 if self.theta is None else self.theta, step)
 
-    def finish(self, comm, final_logweights, synthetic=()):
-        """``(last_weight_stats, counts per step [N + 1] as python ints)``; the log of every rank is read once.
-        ``synthetic``: due steps whose events were skipped on the host because the weights are identically zero."""
-        L = self.log
-        packed = torch.cat([L.stats, L.flags[..., None].double(), L.counts[..., None].double()], dim=-1)
-        h = self.gather_rows_of_ranks(comm, packed).cpu().numpy()  # [N + 1, P, 8]
+    def end_event(self, x, a_next):
+        """Every population resamples (row N of the log), on ``a_next`` clamped at its 0.9 quantile: ``(x, local a_next)``."""
+        a_next = _quantile_clamp(a_next, 0.9, chunk=self.S)
+        return self._launch(x, a_next, 1.0, self.N)[0], a_next
+
+    def gather(self, rows):
+        """[R, Bl, ...] of every rank -> [R, Bg, ...] in population order (one all-gather)."""
+        comm = self.comm
+        if comm.world == 1:
+            return rows
+        g = comm.all_gather(rows.contiguous()).reshape((comm.world,) + tuple(rows.shape))
+        return g.transpose(0, 1).reshape((rows.shape[0], comm.world * rows.shape[1]) + tuple(rows.shape[2:]))
+
+    def finish(self, final_logweights, n_rows):
+        """``(last_weight_stats with arrays [N, P] and log_z [P], counts as python ints)``: one read of every rank's log."""
+        packed = torch.cat([self.stats, self.flags[..., None].double(), self.counts[..., None].double()], dim=-1)
+        h = self.gather(packed).cpu().numpy()  # [N + 1, P, 8]
         N = self.N
-        st, resampled = h[:N, :, :6].copy(), h[:N, :, 6] != 0
-        for s in synthetic:  # ESS = S, mean weight 1, not resampled
-            st[s, :, 1], st[s, :, 2], st[s, :, 3] = 0.0, float(self.S), 1.0
-        tail = logweight_stats(final_logweights.reshape(self.P, self.S))["log_mean_weight"]
-        lmw = st[:, :, 1]
-        # per population the sum _EventLog.finish takes for one: the same numbers in the same order
-        log_z = np.array([lmw[resampled[:, p], p].sum() for p in range(self.P)], np.float64) + tail
-        stats = {"ess": st[:, :, 2].copy(), "ess_fraction": st[:, :, 3].copy(), "log_mean_weight": lmw.copy(),
-                 "resampled": resampled, "n_unique": h[:N, :, 7].astype(np.int64), "log_z": log_z, "populations": self.P}
-        return stats, [int(c) for c in h[:, :, 7].sum(1)]
+        stats = self._weight_stats(h[:N, :, :6].copy(), h[:N, :, 6] != 0, final_logweights)
+        stats.update(n_unique=h[:N, :, 7].astype(np.int64), log_z=stats.pop("log_z"), populations=self.P)
+        return stats, [int(c) for c in h[:n_rows, :, 7].sum(1)]
+
+
+# What is fixed for one integrate_sde call: the rank's shard (walkers off .. off + Bl of Bg, n particles in d dimensions),
+# the noise stream (Philox key, injected normals), the grid and its step table on the host and on the device, the target,
+# the annealing schedule, beta, the resampling interval, the fused backbone (or None), the policy, the MALA parity hooks
+_Run = collections.namedtuple("_Run", "comm off Bl Bg n d mean_free key noise times tab_h tab target schedule beta interval "
+                                      "did_resampling model policy mala_draws")
 
 
 def _terms_from_stats(st4, st8, n_elem, n_walk, computed, debiased):
@@ -458,7 +556,6 @@ class WeightedSDEIntegrator:
         x1 = _lib.dev_tensor(x1, "x1")
         dev = x1.device
         comm = _Comm(self.lightning_module)
-        mala_draws = (mala_noise, mala_uniforms)
         if comm.world > 1 and (mala_noise is not None or mala_uniforms is not None):
             # the hooks are shaped for ONE chain over the whole batch; refuse before the trajectory is integrated
             raise ValueError("mala_noise / mala_uniforms are single-rank parity hooks (world size is "
@@ -484,7 +581,6 @@ class WeightedSDEIntegrator:
             noise = _lib.dev_tensor(noise, "noise")[:, off:off + Bl].contiguous()
         key = self._key(0)
         self._runs += 1
-        u_iter = iter(resample_u) if resample_u is not None else None
 
         start = max(0, min(self.start_resampling_step, N))  # before `start` walkers do not move (:278-280)
         if start > 0 and mean_free:
@@ -492,119 +588,91 @@ class WeightedSDEIntegrator:
         did_resampling = resampling_interval != -1 and resampling_interval < N
         events = [] if resampling_interval == -1 else [
             s for s in range(start, min(self.end_resampling_step, N)) if (s + 1) % resampling_interval == 0]
-        num_unique_idxs = [Bg] * N
         sde_terms_all = []
         st4 = None if self.record_terms else torch.zeros(N, 4, dtype=torch.float64, device=dev)
-        model = self._backbone()
-        pop = None
-        if self.populations is not None:
-            at_end = self.resample_at_end and did_resampling
-            pop = _PopulationRun(comm, Bg, self.populations, batch_size, N, len(events) + int(at_end), resample_u, dev)
-            u_iter = None
-        if getattr(self.sde, "debias_inference", False):
-            return self._integrate_debiased(x, comm, tab_h, times, noise, key, off, Bl, Bg, n, d, mean_free,
-                                            energy_function, annealing_factor_schedule, inverse_temperature,
-                                            resampling_interval, u_iter, mala_draws, pop)
+        debiased = bool(getattr(self.sde, "debias_inference", False))
+        if self.populations is None:
+            policy = _GlobalEvents(comm, Bg, Bl, N, self.ess_threshold, resample_u, dev, debiased, self.batch_size or Bl)
+        else:
+            n_events = len(events) + int(self.resample_at_end and did_resampling)
+            policy = _PopulationEvents(comm, Bg, self.populations, batch_size, N, n_events, self.ess_threshold,
+                                       resample_u, dev, debiased)
+        run = _Run(comm, off, Bl, Bg, n, d, mean_free, key, noise, times, tab_h, tab, energy_function,
+                   annealing_factor_schedule, inverse_temperature, resampling_interval, did_resampling, self._backbone(),
+                   policy, (mala_noise, mala_uniforms))
+        if debiased:
+            x, a, logweights, sde_terms_all = self._integrate_debiased(run, x)
+        else:
+            a = None  # the log-weights are identically zero (drift_A = 0)
+            events = policy.skip_zero_weight_events(events)
+            s = start
+            for stop in events + [N - 1]:  # run steps s..stop inclusive, then (maybe) resample
+                if stop < s:
+                    continue
+                self._run_steps(run, x, s, stop + 1, sde_terms_all, st4)
+                s = stop + 1
+                if stop in events:
+                    x, _ = policy.event(x, None, stop)
+                    if mean_free:
+                        x = remove_mean(x, n, d)
+            # a stride-0 view avoids N*B*4 bytes (reference stacks N copies)
+            logweights = torch.zeros(1, Bg, device=dev).expand(N, Bg)
+            if st4 is not None:
+                # moments come from the world * Bl walkers that are integrated (Bg % world walkers are dropped, :227)
+                sde_terms_all = _terms_from_stats(comm.all_reduce_sum(st4), None, comm.world * Bl * x1.shape[1],
+                                                  comm.world * Bl, [k >= start for k in range(N)], False)
+        x, logweights, counts = self._finish_weights(run, x, a, logweights)
+        x, acceptance_rate_list = self._post_process(run, x)
+        return x, logweights, _host_counts(counts), sde_terms_all, acceptance_rate_list
 
-        due = events
-        if self.ess_threshold is not None and self.ess_threshold < 1.0:
-            # the weights are identically zero here, so ESS = B at every due event: none of them resamples (decided on the
-            # host, no kernel); their uniforms are still drawn, as the fixed schedule would draw them
-            if pop is not None:
-                pop.next_event += len(events)  # a run's uniforms are drawn up front
-            else:
-                for _ in events:
-                    comm.shared_uniform(next(u_iter) if u_iter is not None else None)
-            events = []
-        s = start
-        bounds = events + [N - 1]
-        for stop in bounds:  # run steps s..stop inclusive, then (maybe) resample
-            if stop < s:
-                continue
-            self._run_steps(model, x, tab, tab_h, s, stop + 1, noise, key, off, n, d, mean_free, inverse_temperature,
-                            sde_terms_all, st4)
-            s = stop + 1
-            if stop in events and pop is not None:
-                x, _ = pop.event(x, torch.zeros(Bl, device=dev), 1.0, stop)  # this rank's populations, no collective
-                if mean_free:
-                    x = remove_mean(x, n, d)
-            elif stop in events:
-                a = torch.zeros(comm.world * Bl, device=dev)  # drift_A = 0 in the not-debiased regime
-                u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
-                ids, _ = sample_cat_sys(a.shape[0], a, u)
-                num_unique_idxs[stop] = _count_distinct(ids)
-                x = comm.exchange_rows(x, ids, Bl)
-                if mean_free:
-                    x = remove_mean(x, n, d)
-        # log-weights are identically zero here; a stride-0 view avoids N*B*4 bytes (reference stacks N copies)
-        logweights = torch.zeros(1, Bg, device=dev).expand(N, Bg)
-        if st4 is not None:
-            # moments come from the world * Bl walkers that are integrated (Bg % world walkers are dropped, :227)
-            sde_terms_all = _terms_from_stats(comm.all_reduce_sum(st4), None, comm.world * Bl * x1.shape[1],
-                                              comm.world * Bl, [k >= start for k in range(N)], False)
+    def _finish_weights(self, run, x, a, logweights):
+        """After the trajectory: the end-of-run reweighting when asked for, its row appended, the policy's ``finish``.
+        ``logweights``: rows as the policy collected them, or (``a`` None) identically zero over the global batch."""
+        policy = run.policy
+        if self.resample_at_end and run.did_resampling:
+            x, a_next = self._resample_at_end(run, x, a)
+            logweights = torch.cat([logweights, policy.gather(a_next[None]) if a is None else a_next[None]])
+        if a is not None:
+            logweights = policy.gather(logweights)
+        self.last_weight_stats, counts = policy.finish(logweights[-1], len(logweights))
+        return x, logweights, counts
 
-        if self.resample_at_end and did_resampling:
-            x, a_next, n_unique = self._resample_at_end(x, None, comm, times, energy_function, annealing_factor_schedule,
-                                                        inverse_temperature, u_iter, off, Bl, pop)
-            if pop is not None:
-                a_next = pop.gather_rows_of_ranks(comm, a_next[None])[0]
-            logweights = torch.cat([logweights, a_next[None]])
-            num_unique_idxs.append(n_unique)
-        if pop is not None:
-            self.last_weight_stats, counts = pop.finish(comm, logweights[-1], synthetic=[] if events else due)
-            num_unique_idxs = counts[:len(num_unique_idxs)]
-        elif self.ess_threshold is not None:  # zero log-weights at every due event: ESS = B, mean weight 1
-            at = np.zeros(N, dtype=bool)
-            at[due] = True
-            self.last_weight_stats = {
-                "ess": np.where(at, float(comm.world * Bl), np.nan), "ess_fraction": np.where(at, 1.0, np.nan),
-                "log_mean_weight": np.where(at, 0.0, np.nan), "resampled": at & (self.ess_threshold >= 1.0),
-                "log_z": logweight_stats(logweights[-1])["log_mean_weight"]}
-
+    def _post_process(self, run, x):
+        """Negative-time descent, the MALA chain and the all-gather of the final shards: ``(x, acceptance rates)``."""
         if self.num_negative_time_steps > 0:
-            x = self.negative_time_descent(x, energy_function, walker_offset=off)
+            x = self.negative_time_descent(x, run.target, walker_offset=run.off)
+        keep_order = run.policy.keep_order
         acceptance_rate_list = []
         if self.post_mcmc_steps > 0:
             fn = self.metropolis_hastings_mala_adaptive if self.adaptive_mcmc else self.metropolis_hastings_mala
             kw = dict(dt_init=self.dt_negative_time) if self.adaptive_mcmc else {}
-            if pop is not None:
-                kw["keep_order"] = True  # set-aside walkers return to their own rows
-            x, acceptance_rate_list = fn(x, energy_function, return_acceptance_rate=True, walker_offset=off, comm=comm,
-                                         noise=mala_draws[0], uniforms=mala_draws[1], **kw)
-        x = self._gather_final(x, comm, Bl, pop is not None)  # X1: the only collective on the resampling-free path
-        return x, logweights, _host_counts(num_unique_idxs), sde_terms_all, acceptance_rate_list
+            x, acceptance_rate_list = fn(x, run.target, return_acceptance_rate=True, walker_offset=run.off, comm=run.comm,
+                                         noise=run.mala_draws[0], uniforms=run.mala_draws[1], keep_order=keep_order, **kw)
+        # X1: the only collective on the resampling-free path
+        return self._gather_final(x, run.comm, run.Bl, keep_order), acceptance_rate_list
 
     # ------------------------------------------------------------------ debiased regime (per step; section 8(f) N1)
-    def _integrate_debiased(self, x, comm, tab_h, times, noise, key, off, Bl, Bg, n, d, mean_free, energy_function,
-                            gamma_schedule, beta, resampling_interval, u_iter, mala_draws=(None, None), pop=None):
+    def _integrate_debiased(self, run, x):
         """Feynman-Kac weighted integration (sde_integration.py:131-152,214-297 with sdes.py:151-239): per step the
-        drift of x and of the log-weights a per inference chunk, Euler-Maruyama update, window gates, global
-        systematic resampling when due.  Resampling is global like the reference's: weights and walkers are
-        all-gathered at every resampling event.  With ``pop`` (``populations``) every population of the rank resamples on
-        its own: no collective in the loop, the log-weights stay local and are gathered once after it."""
+        drift of x and of the log-weights a per inference chunk, Euler-Maruyama update, window gates, the policy's event
+        when due.  Returns ``(x, a, log-weight rows as the policy collects them, sde_terms_all)``."""
         N = self.num_integration_steps
         dev = x.device
         L = _lib.lib()
-        zero_a = torch.zeros(Bl, device=dev)  # never written to: every update of `a` makes a new tensor
-        adaptive = _EventLog(N, comm.world * Bl, dev) if self.ess_threshold is not None and pop is None else None
-        a = zero_a
-        logweights, num_unique_idxs, sde_terms_all = [], [], []
-        bs = pop.chunk if pop is not None else self.batch_size or Bl
-        collect = comm.all_gather if pop is None else (lambda v: v)  # a run with populations gathers once, after the loop
-        st4 = st8 = None
-        if not self.record_terms:
-            st4 = torch.zeros(N, 4, dtype=torch.float64, device=dev)
-            st8 = torch.zeros(N, 8, dtype=torch.float64, device=dev)
+        comm, policy, Bl, n, d, off, key, noise = run.comm, run.policy, run.Bl, run.n, run.d, run.off, run.key, run.noise
+        a = zero_a = policy.zero_a
+        logweights, sde_terms_all = [], []
+        st4, st8 = (None, None) if self.record_terms else (torch.zeros(N, 4, dtype=torch.float64, device=dev),
+                                                            torch.zeros(N, 8, dtype=torch.float64, device=dev))
         st = _lib.stream_ptr(dev)
         # this run's _key(PROBE_STREAM_ID): `key` is its _key(0)
         probe_seed = (key + PROBE_STREAM_ID) & 0xFFFFFFFFFFFFFFFF
         for step in range(N):
-            t = times[step]  # host scalar: the schedules' scalars (gamma, dgamma/dt) are then read without a device sync
-            row = tab_h[step]
+            t = run.times[step]  # host scalar: the schedules' scalars (gamma, dgamma/dt) are then read without a device sync
+            row = run.tab_h[step]
             if step < self.start_resampling_step:  # walkers frozen, weights zero (:278-280)
                 a = zero_a
-                logweights.append(collect(a))
-                num_unique_idxs.append(Bg)
+                logweights.append(policy.collect(a))
                 continue
             # one set of launches for the rank's whole shard; the quantile clamp keeps its per-chunk meaning
             kw = {}
@@ -612,7 +680,8 @@ class WeightedSDEIntegrator:
                 # keyed like the noise -- by run, GLOBAL walker index and step --: bitwise repeatable, independent of the
                 # number of ranks, and the two copies of a resampled parent draw different probes
                 kw["probe_key"] = (probe_seed, off, step)
-            terms = self.sde.f(t, x, beta, gamma_schedule, None, energy_function, resampling_interval, clamp_chunk=bs, **kw)
+            terms = self.sde.f(t, x, run.beta, run.schedule, None, run.target, run.interval,
+                               clamp_chunk=policy.clamp_chunk, **kw)
             drift = terms.drift_X.contiguous()
             nz = noise[step].contiguous() if noise is not None else None
             _lib.check(L.pita_em_step(x.data_ptr(), drift.data_ptr(), _lib.ptr(nz), Bl, n, d, float(row[_lib.ST_DT]),
@@ -628,31 +697,11 @@ class WeightedSDEIntegrator:
             a = torch.add(a, terms.drift_A, alpha=float(row[_lib.ST_DT]))  # a + drift_A dt in one launch
             if step >= self.end_resampling_step:
                 a = zero_a
-            n_unique = Bg
-            due = not (resampling_interval == -1 or (step + 1) % resampling_interval != 0
-                       or step >= self.end_resampling_step)
-            if due and pop is not None:
-                x, a = pop.event(x, a, self.ess_threshold, step)
-            elif due and adaptive is not None:
-                # the event is decided on the device: no host read here, every rank decides alike on the gathered vector;
-                # the uniform is drawn whether or not the event resamples (the fixed schedule's stream)
-                ag = comm.all_gather(a)
-                u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
-                ids, resampled, _, n_unique = sample_cat_sys_adaptive(ag.shape[0], ag, self.ess_threshold, u,
-                                                                      out=adaptive.row(step))
-                x = comm.exchange_rows(x, ids, Bl)  # identity ids move nothing
-                a = torch.where(resampled != 0, zero_a, a)
-            elif due:
-                ag = comm.all_gather(a)
-                u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
-                ids, _ = sample_cat_sys(ag.shape[0], ag, u)
-                n_unique = _count_distinct(ids)
-                x = comm.exchange_rows(x, ids, Bl)
-                a = zero_a
-            if mean_free:
+            if not (run.interval == -1 or (step + 1) % run.interval != 0 or step >= self.end_resampling_step):
+                x, a = policy.event(x, a, step)
+            if run.mean_free:
                 x = remove_mean(x, n, d)
-            logweights.append(collect(a))
-            num_unique_idxs.append(n_unique)
+            logweights.append(policy.collect(a))
             if self.record_terms:
                 sde_terms_all.append(terms)
         logweights = torch.stack(logweights)
@@ -660,29 +709,7 @@ class WeightedSDEIntegrator:
             sde_terms_all = _terms_from_stats(comm.all_reduce_sum(st4), comm.all_reduce_sum(st8),
                                               comm.world * Bl * x.shape[1], comm.world * Bl,
                                               [k >= self.start_resampling_step for k in range(N)], True)
-        did_resampling = resampling_interval != -1 and resampling_interval < N
-        if self.resample_at_end and did_resampling:
-            x, a_next, n_unique = self._resample_at_end(x, a, comm, times, energy_function, gamma_schedule, beta, u_iter,
-                                                        off, Bl, pop)
-            logweights = torch.cat([logweights, a_next[None]])
-            num_unique_idxs.append(n_unique)
-        if pop is not None:
-            logweights = pop.gather_rows_of_ranks(comm, logweights)
-            self.last_weight_stats, counts = pop.finish(comm, logweights[-1])
-            num_unique_idxs = counts[:len(num_unique_idxs)]
-        if adaptive is not None:
-            self.last_weight_stats = adaptive.finish(logweights[-1])
-        if self.num_negative_time_steps > 0:
-            x = self.negative_time_descent(x, energy_function, walker_offset=off)
-        acceptance_rate_list = []
-        if self.post_mcmc_steps > 0:
-            fn = self.metropolis_hastings_mala_adaptive if self.adaptive_mcmc else self.metropolis_hastings_mala
-            kw = dict(dt_init=self.dt_negative_time) if self.adaptive_mcmc else {}
-            if pop is not None:
-                kw["keep_order"] = True  # set-aside walkers return to their own rows
-            x, acceptance_rate_list = fn(x, energy_function, return_acceptance_rate=True, walker_offset=off, comm=comm,
-                                         noise=mala_draws[0], uniforms=mala_draws[1], **kw)
-        return self._gather_final(x, comm, Bl, pop is not None), logweights, _host_counts(num_unique_idxs), sde_terms_all, acceptance_rate_list
+        return x, a, logweights, sde_terms_all
 
     def _gather_final(self, x, comm, Bl, keep_order=False):
         """All-gather of the final shards.  After MALA every shard is [its valid walkers, its set-aside walkers]; the
@@ -699,50 +726,38 @@ class WeightedSDEIntegrator:
         tail = [torch.arange(r * Bl + nv[r], (r + 1) * Bl) for r in range(comm.world)]
         return xg[torch.cat(head + tail).to(xg.device)]
 
-    def _resample_at_end(self, x, a, comm, times, energy_function, gamma_schedule, beta, u_iter, off, Bl, pop=None):
+    def _resample_at_end(self, run, x, a):
         """End-of-trajectory reweighting (sde_integration.py:158-183): a_next = log p_target(x) + gamma E_theta(h(t_end), x)
-        (+ the running log-weights a), clamped at its 0.9 quantile, then global systematic resampling.
-        Returns (local slice of the resampled walkers, a_next over the global batch, number of distinct parents).  With
-        ``pop`` the clamp and the resampling are per population and rank-local; a_next is then this rank's and the number
-        of distinct parents is read from the run's log (row N)."""
-        t_end = times[min(self.end_resampling_step, self.num_integration_steps - 1)]
+        (+ the running log-weights a), then the policy's ``end_event``: (this rank's resampled walkers, its row a_next)."""
+        t_end = run.times[min(self.end_resampling_step, self.num_integration_steps - 1)]
         # every rank evaluates its own shard (the reference evaluates the gathered batch on every rank); only the
         # log-weights are gathered, the walkers move in the exchange
         tb = torch.full((x.shape[0],), float(t_end), device=x.device)
-        model_energy = self.sde.energy_net.forward_energy(self.sde.noise_schedule.h(tb), x, beta,
+        model_energy = self.sde.energy_net.forward_energy(self.sde.noise_schedule.h(tb), x, run.beta,
                                                           pin=bool(getattr(self.sde, "pin_energy", False)),
-                                                          energy_function=energy_function, t=tb)  # :166-173
-        a_next = energy_function(x) + model_energy * _scalar(gamma_schedule.gamma(t_end))
+                                                          energy_function=run.target, t=tb)  # :166-173
+        a_next = run.target(x) + model_energy * _scalar(run.schedule.gamma(t_end))
         if a is not None:
             a_next = a_next + a
-        if pop is not None:
-            a_next = _lib.dev_tensor(a_next, "a_next").clone()
-            _lib.check(_lib.lib().pita_quantile_clamp(a_next.data_ptr(), a_next.shape[0], pop.S, 0.9,
-                                                      _lib.stream_ptr(a_next.device)), "pita_quantile_clamp")
-            x, _ = pop.event(x, a_next, 1.0, pop.N)
-            return x, a_next, None
-        a_next = _quantile_clamp(comm.all_gather(a_next.contiguous()), 0.9)
-        u = comm.shared_uniform(next(u_iter) if u_iter is not None else None)
-        ids, _ = sample_cat_sys(a_next.shape[0], a_next, u)
-        x = comm.exchange_rows(x, ids, Bl)
-        return x, a_next, _count_distinct(ids)
+        return run.policy.end_event(x, a_next)
 
     # ------------------------------------------------------------------ A2-A4 steps [s0, s1)
-    def _run_steps(self, model, x, tab, tab_h, s0, s1, noise, key, off, n, d, mean_free, beta, sde_terms_all, st4=None):
+    def _run_steps(self, run, x, s0, s1, sde_terms_all, st4=None):
         if s1 <= s0:
             return
+        model, noise, key, off, n, d, mean_free = run.model, run.noise, run.key, run.off, run.n, run.d, run.mean_free
         if model is not None and not self.record_terms and (not hasattr(model, "can_fuse") or model.can_fuse(n, d)):
             nz = noise[s0:s1].contiguous() if noise is not None else None
-            model.sampler_run(x, tab[s0:s1].contiguous(), s1 - s0, noise=nz, seed=key, walker_offset=off, step0=s0,
+            model.sampler_run(x, run.tab[s0:s1].contiguous(), s1 - s0, noise=nz, seed=key, walker_offset=off, step0=s0,
                               remove_mean=mean_free, n_particles=n, n_dim=d,
                               stats_out=st4[s0:s1] if st4 is not None else None)
             return
         # per-step path: any backbone with forward(t, x, beta); drift through ScoreNet, update by pita_em_step
         L = _lib.lib()
         for k in range(s0, s1):
-            row = tab_h[k]
+            row = run.tab_h[k]
             ht = torch.full((x.shape[0],), float(row[_lib.ST_H]), device=x.device)
-            score = self.sde.score_net(ht, x, beta)
+            score = self.sde.score_net(ht, x, run.beta)
             drift = float(row[_lib.ST_GAMMA]) * (score * float(row[_lib.ST_G2]))
             drift = drift.contiguous()
             nz = noise[k].contiguous() if noise is not None else None

@@ -5,18 +5,27 @@ import torch
 from . import _lib
 
 
+def _uniform0(u):
+    """An event's uniform as a Python float; None draws one float64 from torch's CPU generator, like the reference."""
+    if u is None:
+        u = torch.rand(size=(1,), dtype=torch.float64)
+    return float(u.reshape(-1)[0]) if isinstance(u, torch.Tensor) else float(u)
+
+
+def _workspace(nbytes, device):
+    """8-byte aligned device scratch of at least ``nbytes`` bytes."""
+    return torch.empty((int(nbytes) + 7) // 8, device=device, dtype=torch.float64)
+
+
 def sample_cat_sys(bs, logits, u=None):
     """ids[bs] (int64 device tensor) for systematic resampling of ``softmax(logits)`` clipped to
     [1e-6, 1] (not renormalised).  ``u`` defaults to one float64 uniform from torch's CPU
     generator, exactly like the reference.  Returns ``(ids, None)`` like the reference."""
     logits = _lib.dev_tensor(logits, "logits").reshape(-1)
     assert logits.shape[0] == bs
-    if u is None:
-        u = torch.rand(size=(1,), dtype=torch.float64)
-    u0 = float(u.reshape(-1)[0]) if isinstance(u, torch.Tensor) else float(u)
+    u0 = _uniform0(u)
     ids = torch.empty(bs, device=logits.device, dtype=torch.int64)
-    nbytes = int(_lib.lib().pita_resample_workspace_bytes(bs))
-    ws = torch.empty((nbytes + 7) // 8, device=logits.device, dtype=torch.float64)  # 8-byte aligned scratch
+    ws = _workspace(_lib.lib().pita_resample_workspace_bytes(bs), logits.device)
     _lib.check(_lib.lib().pita_systematic_resample(logits.data_ptr(), bs, u0, ids.data_ptr(), ws.data_ptr(),
                                                    _lib.stream_ptr(logits.device)), "pita_systematic_resample")
     return ids, None
@@ -33,9 +42,7 @@ def sample_cat_sys_adaptive(bs, logits, theta, u=None, out=None):
     ``(resampled, stats, n_unique)`` to write into (rows of a caller's per-step buffers)."""
     logits = _lib.dev_tensor(logits, "logits").reshape(-1)
     assert logits.shape[0] == bs
-    if u is None:
-        u = torch.rand(size=(1,), dtype=torch.float64)
-    u0 = float(u.reshape(-1)[0]) if isinstance(u, torch.Tensor) else float(u)
+    u0 = _uniform0(u)
     dev = logits.device
     ids = torch.empty(bs, device=dev, dtype=torch.int64)
     if out is None:
@@ -43,8 +50,7 @@ def sample_cat_sys_adaptive(bs, logits, theta, u=None, out=None):
                torch.empty((), device=dev, dtype=torch.int64))
     resampled, stats, n_unique = out
     L = _lib.lib()
-    nbytes = int(L.pita_adaptive_resample_workspace_bytes(bs))
-    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)  # 8-byte aligned scratch
+    ws = _workspace(L.pita_adaptive_resample_workspace_bytes(bs), dev)
     _lib.check(L.pita_adaptive_resample(logits.data_ptr(), bs, u0, float(theta), ids.data_ptr(), n_unique.data_ptr(),
                                         stats.data_ptr(), resampled.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),
                "pita_adaptive_resample")
@@ -90,8 +96,7 @@ def sample_cat_sys_populations(logits, n_pop, theta, u=None, out=None):
                torch.empty(n_pop, device=dev, dtype=torch.int64))
     resampled, stats, n_unique = out
     L = _lib.lib()
-    nbytes = int(L.pita_population_resample_workspace_bytes(n_pop, S))
-    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)  # 8-byte aligned scratch
+    ws = _workspace(L.pita_population_resample_workspace_bytes(n_pop, S), dev)
     _lib.check(L.pita_population_resample(logits.data_ptr(), n_pop, S, u.data_ptr(), float(theta), ids.data_ptr(),
                                           n_unique.data_ptr(), stats.data_ptr(), resampled.data_ptr(),
                                           logw_next.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),

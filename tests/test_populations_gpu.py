@@ -197,13 +197,15 @@ def lj13(pa, golden):
     x1 = (O.remove_mean(torch.randn(B, 39, generator=gen), 13, 3) * 80.0).cuda()
     noise = torch.randn(LJ_STEPS, B, 39, generator=gen).cuda()
 
-    def run(populations, ess_threshold, resample_u, debias=True):
+    def run(populations, ess_threshold, resample_u, debias=True, at_end=False):
         sde = pa.VEReverseSDE(noise_schedule=sched, score_net=pa.ScoreNet(net), energy_net=EnergyNet(copy.deepcopy(net)),
                               debias_inference=debias)
         integ = pa.WeightedSDEIntegrator(sde=sde, num_integration_steps=LJ_STEPS, start_resampling_step=0,
                                          end_resampling_step=LJ_STEPS, resampling_interval=2, num_negative_time_steps=0,
-                                         post_mcmc_steps=0, seed=3, ess_threshold=ess_threshold, populations=populations)
-        x, logw, counts, _, _ = integ.integrate_sde(x1, _Geometry(), pa.ConstantAnnealingFactorSchedule(4 / 3),
+                                         post_mcmc_steps=0, seed=3, ess_threshold=ess_threshold, populations=populations,
+                                         resample_at_end=at_end)
+        target = pa.LennardJonesEnergy(39, 13, 3) if at_end else _Geometry()  # the end-of-run reweighting evaluates it
+        x, logw, counts, _, _ = integ.integrate_sde(x1, target, pa.ConstantAnnealingFactorSchedule(4 / 3),
                                                     inverse_temperature=1.0, noise=noise, resample_u=resample_u)
         return x, logw, counts, integ.last_weight_stats
 
@@ -277,6 +279,30 @@ def test_one_population_is_the_default(pa, lj13, monkeypatch, ess_threshold, deb
         assert s1["log_z"][0] == s0["log_z"]
         for k in ("ess", "ess_fraction", "log_mean_weight", "resampled"):
             assert np.array_equal(s1[k][:, 0], s0[k], equal_nan=k != "resampled"), k
+
+
+def test_one_population_is_the_default_with_resample_at_end(pa, lj13):
+    """The default regime (log-weights identically zero until the end) with ``resample_at_end``: populations=1 equals
+    populations=None bit for bit, a threshold of 1 is the fixed schedule, and its events are the due steps."""
+    N, U = LJ_STEPS, LJ_U + [[0.62, 0.33, 0.08]]  # four due events and the one at the end
+    due = np.arange(N) % 2 == 1
+    runs = {}
+    for ess_threshold in (None, 0.6, 1.0):
+        one = lj13(1, ess_threshold, [[u[0]] for u in U], False, at_end=True)
+        none = lj13(None, ess_threshold, [u[0] for u in U], False, at_end=True)
+        assert one[1].shape == (N + 1, 3 * LJ_S) and len(one[2]) == N + 1
+        assert torch.equal(bits(one[0]), bits(none[0])) and torch.equal(bits(one[1]), bits(none[1])) and one[2] == none[2]
+        s1, s0 = one[3], none[3]
+        assert s1["populations"] == 1 and (s0 is None) == (ess_threshold is None)
+        if s0 is not None:
+            assert s1["log_z"][0] == s0["log_z"]
+            for k in ("ess", "ess_fraction", "log_mean_weight", "resampled"):
+                assert np.array_equal(s1[k][:, 0], s0[k], equal_nan=k != "resampled"), (ess_threshold, k)
+        runs[ess_threshold] = (one, none)
+    for always, fixed in zip(runs[1.0], runs[None]):
+        assert torch.equal(bits(always[0]), bits(fixed[0])) and torch.equal(bits(always[1]), bits(fixed[1]))
+        assert always[2] == fixed[2]
+    assert np.array_equal(runs[1.0][0][3]["resampled"][:, 0], due) and np.array_equal(runs[1.0][1][3]["resampled"], due)
 
 
 def _gmm_sde(pa, golden):

@@ -1,12 +1,23 @@
-"""Whole debiased integrate_sde (Feynman-Kac weights, resampling every step) at 65 536 walkers: per-step wall time."""
-import copy, sys, time
+"""Whole debiased integrate_sde (Feynman-Kac weights, without resampling and with an event every step) at 65 536 walkers:
+per-step wall time.  At 2 048 walkers the host side of the loop dominates: that is the shape for host-cost comparisons.
+python tools/time_debiased_integrate.py [walkers] [steps] [--intervals -1,1] [--ess-threshold T] [--reps R] [--root DIR]
+``--reps``: timed calls after the warm-up call, the median is printed; ``--root``: the tree whose pita_amd is imported."""
+import argparse, copy, os, sys, time
 import numpy as np, torch
-sys.path.insert(0, ".")
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ap = argparse.ArgumentParser()
+ap.add_argument("walkers", nargs="?", type=int, default=65536)
+ap.add_argument("steps", nargs="?", type=int, default=200)  # a real grid: ten steps over the whole schedule throw walkers out of the f16 range
+ap.add_argument("--intervals", default="-1,1")
+ap.add_argument("--ess-threshold", type=float, default=None)
+ap.add_argument("--reps", type=int, default=1)
+ap.add_argument("--root", default=HERE)
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
 import pita_amd
 from pita_amd.energy_net import EnergyNet
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 200  # a real grid: ten steps over the whole schedule throw walkers out of the f16 range
-w = dict(np.load("tests/golden/egnn_weights_trainedlike.npz"))
+B, N = args.walkers, args.steps
+w = dict(np.load(os.path.join(HERE, "tests", "golden", "egnn_weights_trainedlike.npz")))
 net = pita_amd.EGNN_dynamics(13, 3, hidden_nf=32, n_layers=3, recurrent=True, tanh=True, attention=True,
                              condition_time=True, condition_temperature=True, agg="sum")
 net.load_state_dict({k: torch.tensor(v) for k, v in w.items()})
@@ -15,13 +26,17 @@ sde = pita_amd.VEReverseSDE(noise_schedule=sched, score_net=pita_amd.ScoreNet(ne
                             debias_inference=True)
 gam = pita_amd.ConstantAnnealingFactorSchedule(4 / 3)
 e = pita_amd.LennardJonesEnergy(39, 13, 3)
-for interval in (-1, 1):
+for interval in (int(v) for v in args.intervals.split(",")):
     integ = pita_amd.WeightedSDEIntegrator(sde=sde, num_integration_steps=N, start_resampling_step=0, end_resampling_step=N,
                                            resampling_interval=interval, num_negative_time_steps=0, post_mcmc_steps=0,
-                                           batch_size=512)
+                                           batch_size=512, ess_threshold=args.ess_threshold)
     x1 = pita_amd.Prior(scale=3.0, n_particles=13, spatial_dim=3).sample(B)
     integ.integrate_sde(x1, e, gam, inverse_temperature=1.0); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    x, logw, uniq, _, _ = integ.integrate_sde(x1, e, gam, inverse_temperature=1.0); torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"interval={interval}: {dt/N*1e3:.1f} ms per step, {B*N/dt:.3e} walker-steps/s, unique[-1]={uniq[-1]}")
+    dts = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        x, logw, uniq, _, _ = integ.integrate_sde(x1, e, gam, inverse_temperature=1.0); torch.cuda.synchronize()
+        dts.append(time.perf_counter() - t0)
+    dt = float(np.median(dts))
+    print(f"interval={interval} ess_threshold={args.ess_threshold}: {dt/N*1e3:.4f} ms per step (median of {args.reps}), "
+          f"{B*N/dt:.3e} walker-steps/s, unique[-1]={uniq[-1]}")

@@ -11,18 +11,26 @@
     integrate_sde of P x 2 048 walkers with populations=P against P consecutive integrate_sde calls of 2 048 walkers
     (populations=None), alternating, host wall time between two synchronisations -- the host work of a run is part of what
     a user waits for --, in ms per population-step (time / (P * steps)); median [min, max].
-usage: python tools/time_populations.py [reps] [rounds] [steps]; the committed profile is the second of two runs."""
-import copy, os, sys, time
+usage: python tools/time_populations.py [reps] [rounds] [steps] [--pops 1,8,32] [--integrate-only] [--root DIR]; the
+committed profile is the second of two runs.  ``--integrate-only``: (b) alone, for every P of ``--pops``; ``--root``: the
+tree whose pita_amd is imported (host-cost comparisons of two trees on one library)."""
+import argparse, copy, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+ap = argparse.ArgumentParser()
+ap.add_argument("reps", nargs="?", type=int, default=1000)
+ap.add_argument("rounds", nargs="?", type=int, default=7)
+ap.add_argument("steps", nargs="?", type=int, default=8)
+ap.add_argument("--pops", default="1,8,32")
+ap.add_argument("--integrate-only", action="store_true")
+ap.add_argument("--root", default=ROOT)
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
 import pita_amd as pa
 from pita_amd.energy_net import EnergyNet
 L, D, S = pa._lib.lib(), 39, 2048
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 8
-POPS = (1, 8, 32)
+reps, rounds, steps = args.reps, args.rounds, args.steps
+POPS = tuple(int(v) for v in args.pops.split(","))
 
 
 def cell(v):
@@ -33,7 +41,7 @@ print(f"(a) one resampling event of P x {S} walkers, D = {D}, log-weights N(0, 1
       f"{rounds} windows of {reps} events")
 print(f"{'P':>3} {'B':>6} {'fixed':>26} {'adaptive th=1':>26} {'adaptive th=0':>26} {'populations th=1':>26} "
       f"{'populations th=0':>26}  pop1/fixed  pop1/adaptive1  pop0/adaptive0")
-for P in POPS:
+for P in () if args.integrate_only else POPS:
     B = P * S
     a = torch.from_numpy(np.concatenate([np.float32(np.random.default_rng(3000 + p).standard_normal(S)) for p in range(P)])).cuda()
     u = torch.from_numpy(np.random.default_rng(7).random(P)).cuda()
@@ -118,7 +126,7 @@ def run(x1, populations):
     return integ.integrate_sde(x1, Geometry(), gam, inverse_temperature=1.0)
 
 
-for P in POPS[1:]:
+for P in POPS if args.integrate_only else POPS[1:]:
     x1 = pa.Prior(scale=3.0, n_particles=13, spatial_dim=3, seed=2).sample(P * S)
     parts = [x1[p * S:(p + 1) * S].contiguous() for p in range(P)]
     together = lambda: run(x1, P)
