@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libpita_hip.so")
 
 STEP_STRIDE = 16
 ABI_VERSION = 13
+PITA_EUNSUPPORTED = -2  # include/pita_hip.h: no kernel serves these arguments (callers with another route take it)
 ST_CS, ST_CIN, ST_COUT, ST_CNOISE, ST_H, ST_G2, ST_GAMMA, ST_DT, ST_NOISE_SCALE, ST_SQRT_DT, ST_BETA = range(11)
 
 

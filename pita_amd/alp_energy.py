@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._target import HipTarget
 from .base_energy_function import BaseMoleculeEnergy
 
 KB_KJ_PER_MOL_K = 8.314462618e-3
@@ -95,7 +96,7 @@ def tables_from_openmm_xml(source):
     return {k: np.asarray(v) for k, v in t.items()}, opts
 
 
-class ForceFieldEnergy(BaseMoleculeEnergy):
+class ForceFieldEnergy(HipTarget, BaseMoleculeEnergy):
     def __init__(self, tables, n_particles, spatial_dim=3, temperature=300.0, data_normalization_factor=1.0,
                  cutoff=None, rf_dielectric=78.3, device="cuda", is_molecule=True, gb_solute_dielectric=1.0,
                  gb_solvent_dielectric=78.5, gb_surface_area_factor=28.3919551, **kwargs):
@@ -164,46 +165,21 @@ class ForceFieldEnergy(BaseMoleculeEnergy):
             pass
 
     def __call__(self, samples: torch.Tensor, return_force=False):
-        x = _lib.dev_tensor(samples, "samples").reshape(-1, self._dimensionality)
-        B = x.shape[0]
-        logp = torch.empty(B, device=x.device, dtype=torch.float32)
-        force = torch.empty_like(x) if return_force else None
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().pita_ff_logp_force(self._native(), x.data_ptr(), logp.data_ptr(), _lib.ptr(force), B,
-                                                     _lib.stream_ptr(x.device)), "pita_ff_logp_force")
-        return (logp, force) if return_force else logp
-
+        return self._logp_force_call("pita_ff_logp_force", self._samples(samples), return_force=return_force)
 
     def fused_descent(self, x, num_steps, dt, noise_scale, sqrt_dt, seed=0, walker_offset=0, step0=0, remove_mean=True,
                       noise=None):
-        """``num_steps`` of x <- remove_mean(x + F dt + noise_scale*sqrt_dt*xi) in ONE launch, in place
-        (negative_time_descent, sde_integration.py:353-360; pita_ff_descent), bit-identical to the per-step path."""
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().pita_ff_descent(
-                self._native(), x.data_ptr(), _lib.ptr(noise), x.shape[0], int(num_steps), float(dt), float(noise_scale),
-                float(sqrt_dt), int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), int(step0), int(bool(remove_mean)),
-                _lib.stream_ptr(x.device)), "pita_ff_descent")
-        return x
+        """The fused descent of the table in _target.py (pita_ff_descent), bit-identical to the per-step path."""
+        return self._descent_call("pita_ff_descent", x, noise, (), num_steps, dt, noise_scale, sqrt_dt, seed, walker_offset,
+                                  step0, remove_mean)
 
     def fused_mala(self, x, logp, num_steps, dt_dev, adaptive, total, noise=None, uniforms=None, seed=0, walker_offset=0,
                    walker_ids=None, step0=0, remove_mean=True, rates_out=None):
-        """All ``num_steps`` MALA steps in place on ``x`` / ``logp`` / ``dt_dev`` (pita_ff_mala;
-        metropolis_hastings_mala(_adaptive), sde_integration.py:362-470), bit-identical to the launch-per-kernel path:
-        one launch for a non-adaptive chain, one per step for an adaptive one, no grid barrier in either.  Returns ``x``
-        when the launch ran, None when the handle's launch plan cannot hold the chain (PITA_EUNSUPPORTED): the caller
-        then runs the launch-per-kernel path.  The whole batch goes in one grid-striding launch (``energy_batch_size``
-        of ALPEnergy only chunks ``__call__``; a walker's result does not depend on its batch)."""
-        L = _lib.lib()
-        ws = torch.empty((int(L.pita_ff_mala_workspace_bytes(int(num_steps))) + 7) // 8, device=x.device, dtype=torch.int64)
-        with torch.cuda.device(x.device):
-            rc = L.pita_ff_mala(self._native(), x.data_ptr(), logp.data_ptr(), _lib.ptr(noise), _lib.ptr(uniforms),
-                                x.shape[0], int(num_steps), dt_dev.data_ptr(), int(bool(adaptive)), int(total),
-                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(walker_offset), _lib.ptr(walker_ids), int(step0),
-                                int(bool(remove_mean)), _lib.ptr(rates_out), ws.data_ptr(), _lib.stream_ptr(x.device))
-        if rc == -2:  # PITA_EUNSUPPORTED
-            return None
-        _lib.check(rc, "pita_ff_mala")
-        return x
+        """The fused MALA chain of the table in _target.py (pita_ff_mala); None when the handle's launch plan cannot hold the
+        chain (PITA_EUNSUPPORTED).  The whole batch goes in one grid-striding launch (``energy_batch_size`` of ALPEnergy
+        only chunks ``__call__``; a walker's result does not depend on its batch)."""
+        return self._mala_call("pita_ff_mala", "pita_ff_mala_workspace_bytes", x, logp, (), num_steps, dt_dev, adaptive,
+                               total, noise, uniforms, seed, walker_offset, walker_ids, step0, remove_mean, rates_out)
 
 
 class ALPEnergy(ForceFieldEnergy):

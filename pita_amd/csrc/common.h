@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include <cstdarg>
@@ -69,6 +70,65 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes) {
   const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e == hipSuccess) m[kernel] = bytes;
   return e;
+}
+
+// Compute units of the current device; the first call per device asks HIP, later calls read the cache.
+inline int device_cus(int& cus) {
+  static PerDevice<int> cached;
+  int& n = cached.get();
+  if (n == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    PITA_HIP_CHECK(hipGetDevice(&dev));
+    PITA_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    if (prop.multiProcessorCount <= 0) return fail(PITA_EHIP, "device %d reports %d compute units", dev, prop.multiProcessorCount);
+    n = prop.multiProcessorCount;
+  }
+  cus = n;
+  return PITA_OK;
+}
+
+// Resident blocks per compute unit of `kernel` (registers and LDS decide): what the persistent grids multiply by
+// device_cus.  Cached per device and kernel like ensure_dynamic_lds; a failed query or an answer of zero is an error.
+inline int resident_blocks(const void* kernel, int threads, size_t dynamic_lds, int& blocks) {
+  struct Entry { int threads; size_t lds; int blocks; };
+  static std::mutex mu;
+  static std::unordered_map<const void*, Entry> table[kMaxDevices];
+  std::lock_guard<std::mutex> lock(mu);
+  auto& m = table[current_device_slot()];
+  const auto it = m.find(kernel);
+  if (it == m.end() || it->second.threads != threads || it->second.lds != dynamic_lds) {
+    int v = 0;
+    PITA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, threads, dynamic_lds));
+    if (v <= 0) return fail(PITA_EHIP, "a %d-thread block with %zu B of dynamic LDS does not fit a compute unit", threads, dynamic_lds);
+    m[kernel] = Entry{threads, dynamic_lds, v};
+    blocks = v;
+    return PITA_OK;
+  }
+  blocks = it->second.blocks;
+  return PITA_OK;
+}
+template <class K>
+inline int resident_blocks(K* kernel, int threads, size_t dynamic_lds, int& blocks) {
+  return resident_blocks(reinterpret_cast<const void*>(kernel), threads, dynamic_lds, blocks);
+}
+
+// Grid of a grid-striding kernel: one block per tile up to a cap; the fixed caps are kGridCus * k, k set at the call site.
+constexpr long long kGridCus = 256;
+inline unsigned capped_grid(long long tiles, long long cap) { return (unsigned)(tiles < cap ? tiles : cap); }
+
+// Run-time value -> template argument of the kernel a generic lambda f names: f(std::integral_constant<int, D>{}) for d
+// in [1, MAX] (checked by the caller; MAX takes what is left), f(std::true_type{} / std::false_type{}) for a flag.
+template <int MAX, class F>
+inline auto dispatch_dim(int d, F&& f) {
+  if constexpr (MAX > 1) {
+    if (d < MAX) return dispatch_dim<MAX - 1>(d, f);
+  }
+  return f(std::integral_constant<int, MAX>{});
+}
+template <class F>
+inline auto dispatch_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // A handle's scratch buffer grown on demand to at least `bytes` (plus `tail` bytes behind them that the size does not

@@ -893,10 +893,10 @@ static int launch_descent(float* x, const float* noise, int64_t B, int n, int d,
   PITA_REQUIRE(d >= 1 && d <= 3, "descent: n_dim must be 1, 2 or 3");
   hipStream_t s = (hipStream_t)stream;
   if (KIND == E_LJ && n == 13 && d == 3) {
-    const long long nblk = (B + 127) / 128;
-    const unsigned grid = (unsigned)(nblk < 256LL * 4 ? nblk : 256LL * 4);
-    if (p.rm2 == 1.0f) hipLaunchKernelGGL(lj13_descent_kernel<true>, dim3(grid), dim3(256), 0, s, x, noise, (long long)B, p, q);
-    else hipLaunchKernelGGL(lj13_descent_kernel<false>, dim3(grid), dim3(256), 0, s, x, noise, (long long)B, p, q);
+    const unsigned grid = capped_grid((B + 127) / 128, kGridCus * 4);
+    dispatch_bool(p.rm2 == 1.0f, [&](auto unit) {
+      hipLaunchKernelGGL(lj13_descent_kernel<decltype(unit)::value>, dim3(grid), dim3(256), 0, s, x, noise, (long long)B, p, q);
+    });
     PITA_LAUNCH_CHECK();
     return PITA_OK;
   }
@@ -904,28 +904,15 @@ static int launch_descent(float* x, const float* noise, int64_t B, int n, int d,
     const int rc = ring_launch_descent(KIND, x, noise, B, n, d, p, q, stream);
     if (rc != 1) return rc;
   }
-  if (n <= 64) {
-    const int WB = 4 * (64 / n);
-    const long long nblk = (B + WB - 1) / WB;
-    const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
-    const size_t lds = sizeof(float) * (size_t)(2 * WB * n * d + WB * d);
-    switch (d) {
-      case 1: hipLaunchKernelGGL((pair_descent_n3l_kernel<1, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-      case 2: hipLaunchKernelGGL((pair_descent_n3l_kernel<2, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-      default: hipLaunchKernelGGL((pair_descent_n3l_kernel<3, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-    }
-    PITA_LAUNCH_CHECK();
-    return PITA_OK;
-  }
-  const int WB = 256 / n;
-  const long long nblk = (B + WB - 1) / WB;
-  const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
-  const size_t lds = sizeof(float) * (size_t)(WB * n * d);
-  switch (d) {
-    case 1: hipLaunchKernelGGL((pair_descent_kernel<1, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-    case 2: hipLaunchKernelGGL((pair_descent_kernel<2, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-    default: hipLaunchKernelGGL((pair_descent_kernel<3, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q); break;
-  }
+  const bool n3l = n <= 64;  // whole walkers per wavefront (pair_force_n3l)
+  const int WB = n3l ? 4 * (64 / n) : 256 / n;
+  const unsigned grid = capped_grid((B + WB - 1) / WB, kGridCus * 16);
+  const size_t lds = sizeof(float) * (size_t)(n3l ? 2 * WB * n * d + WB * d : WB * n * d);
+  dispatch_dim<3>(d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    if (n3l) hipLaunchKernelGGL((pair_descent_n3l_kernel<D, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q);
+    else hipLaunchKernelGGL((pair_descent_kernel<D, KIND>), dim3(grid), dim3(256), lds, s, x, noise, B, n, WB, p, q);
+  });
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -938,34 +925,20 @@ static int launch_pair(const float* x, float* logp, float* force, int64_t B, int
   PITA_REQUIRE(x && logp, "pair energy: null argument");
   PITA_REQUIRE(n >= 2 && n <= 256, "pair energy: n_particles must be in [2,256]");
   PITA_REQUIRE(d >= 1 && d <= 3, "pair energy: n_dim must be 1, 2 or 3");
-  if (B == 0) return PITA_OK;
   hipStream_t s = (hipStream_t)stream;
   {  // compile-time particle counts (LJ55, DW4): ring_kernels.hip
     const int rc = ring_launch_energy(KIND, x, logp, force, B, n, d, p, stream);
     if (rc != 1) return rc;
   }
-  if (n <= 64) {  // whole walkers per wavefront: unordered pairs with Newton's third law
-    const int WB = 4 * (64 / n);
-    const long long nblk = (B + WB - 1) / WB;
-    const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
-    const size_t lds = sizeof(float) * (size_t)(2 * WB * n * d + WB * n + WB * d);
-    switch (d) {
-      case 1: hipLaunchKernelGGL((pair_energy_n3l_kernel<1, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-      case 2: hipLaunchKernelGGL((pair_energy_n3l_kernel<2, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-      default: hipLaunchKernelGGL((pair_energy_n3l_kernel<3, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-    }
-    PITA_LAUNCH_CHECK();
-    return PITA_OK;
-  }
-  const int WB = 256 / n;
-  const long long nblk = (B + WB - 1) / WB;
-  const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
-  const size_t lds = sizeof(float) * (size_t)(WB * n * d + WB * n);
-  switch (d) {
-    case 1: hipLaunchKernelGGL((pair_energy_kernel<1, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-    case 2: hipLaunchKernelGGL((pair_energy_kernel<2, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-    default: hipLaunchKernelGGL((pair_energy_kernel<3, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p); break;
-  }
+  const bool n3l = n <= 64;  // whole walkers per wavefront: unordered pairs with Newton's third law
+  const int WB = n3l ? 4 * (64 / n) : 256 / n;
+  const unsigned grid = capped_grid((B + WB - 1) / WB, kGridCus * 16);
+  const size_t lds = sizeof(float) * (size_t)(n3l ? 2 * WB * n * d + WB * n + WB * d : WB * n * d + WB * n);
+  dispatch_dim<3>(d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    if (n3l) hipLaunchKernelGGL((pair_energy_n3l_kernel<D, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p);
+    else hipLaunchKernelGGL((pair_energy_kernel<D, KIND>), dim3(grid), dim3(256), lds, s, x, logp, force, B, n, WB, p);
+  });
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -1029,9 +1002,7 @@ extern "C" int pita_lj_smooth_logp_force(const float* x, float* logp, float* for
                                          float osc_scale, float range_min, const float* coef4, void* stream) {
   PITA_REQUIRE(temperature > 0.f, "pita_lj_smooth_logp_force: temperature must be > 0");
   PITA_REQUIRE(coef4 && range_min > 0.f, "pita_lj_smooth_logp_force: spline coefficients / range_min");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.energy_factor = energy_factor; p.dist_eps = dist_eps; p.eps = eps;
-  p.rm2 = rm * rm; p.osc_scale = osc_scale;
+  PairParams p = lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale);
   p.sm_min = range_min; p.sc0 = coef4[0]; p.sc1 = coef4[1]; p.sc2 = coef4[2]; p.sc3 = coef4[3];
   return launch_pair<E_LJS>(x, logp, force, B, n, d, p, stream);
 }
@@ -1040,43 +1011,31 @@ extern "C" int pita_lj_logp_force(const float* x, float* logp, float* force, int
                                   float energy_factor, float dist_eps, float eps, float rm, float osc_scale,
                                   void* stream) {
   PITA_REQUIRE(temperature > 0.f, "pita_lj_logp_force: temperature must be > 0");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.energy_factor = energy_factor; p.dist_eps = dist_eps; p.eps = eps;
-  p.rm2 = rm * rm; p.osc_scale = osc_scale;
-  p.cw = -p.inv_T * (2.0f * energy_factor * eps * 12.0f / p.rm2); p.co = -p.inv_T * osc_scale;
+  const PairParams p = lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale);
   if (n == 13 && d == 3 && B > 0) {
     PITA_REQUIRE(x && logp, "pita_lj_logp_force: null argument");
     if (getenv("PITA_LJ13_RING")) return ring_launch_energy(E_LJ, x, logp, force, B, n, d, p, stream);
     // 2 lanes per walker while the batch cannot fill every SIMD twice with 1 lane per walker
-    const bool two = B <= 256LL * 1024;
-    const int WPB = two ? 128 : 256;
-    const long long nblk = (B + WPB - 1) / WPB;
-    const unsigned grid = (unsigned)(nblk < 256LL * 32 ? nblk : 256LL * 32);
-    const bool unit = p.rm2 == 1.0f;
+    const bool two = B <= 256LL * 1024, unit = p.rm2 == 1.0f;
+    const long long nblk = (B + (two ? 127 : 255)) / (two ? 128 : 256);
     hipStream_t s = (hipStream_t)stream;
-    if (!two && !getenv("PITA_LJ13_NO_STREAM")) {  // persistent blocks with the next tile in flight
-      static PerDevice<int> per_cu_on, n_cu_on;
-      int &per_cu = per_cu_on.get(), &n_cu = n_cu_on.get();
-      if (per_cu == 0) {
-        int dev = 0, v = 0;
-        hipDeviceProp_t prop;
-        PITA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, lj13_stream_kernel<true>, 256, 0));
-        PITA_HIP_CHECK(hipGetDevice(&dev));
-        PITA_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        per_cu = v > 0 ? v : 1;
-        n_cu = prop.multiProcessorCount;
-      }
-      const long long cap = (long long)per_cu * n_cu;
-      const unsigned g2 = (unsigned)(nblk < cap ? nblk : cap);
-      if (unit) hipLaunchKernelGGL(lj13_stream_kernel<true>, dim3(g2), dim3(256), 0, s, x, logp, force, (long long)B, p);
-      else hipLaunchKernelGGL(lj13_stream_kernel<false>, dim3(g2), dim3(256), 0, s, x, logp, force, (long long)B, p);
-      PITA_LAUNCH_CHECK();
-      return PITA_OK;
+    if (!two && !getenv("PITA_LJ13_NO_STREAM")) {  // persistent blocks with the next tile in flight: one residency
+      int per_cu = 0, cus = 0;
+      if (int rc = resident_blocks(lj13_stream_kernel<true>, 256, 0, per_cu)) return rc;
+      if (int rc = device_cus(cus)) return rc;
+      const unsigned grid = capped_grid(nblk, (long long)per_cu * cus);
+      dispatch_bool(unit, [&](auto u) {
+        hipLaunchKernelGGL(lj13_stream_kernel<decltype(u)::value>, dim3(grid), dim3(256), 0, s, x, logp, force, (long long)B, p);
+      });
+    } else {
+      const unsigned grid = capped_grid(nblk, kGridCus * 32);
+      dispatch_bool(two, [&](auto t) {
+        dispatch_bool(unit, [&](auto u) {
+          hipLaunchKernelGGL((lj13_kernel<decltype(t)::value ? 2 : 1, decltype(u)::value>), dim3(grid), dim3(256), 0, s, x, logp,
+                             force, (long long)B, p);
+        });
+      });
     }
-    if (two && unit) hipLaunchKernelGGL((lj13_kernel<2, true>), dim3(grid), dim3(256), 0, s, x, logp, force, (long long)B, p);
-    else if (two) hipLaunchKernelGGL((lj13_kernel<2, false>), dim3(grid), dim3(256), 0, s, x, logp, force, (long long)B, p);
-    else if (unit) hipLaunchKernelGGL((lj13_kernel<1, true>), dim3(grid), dim3(256), 0, s, x, logp, force, (long long)B, p);
-    else hipLaunchKernelGGL((lj13_kernel<1, false>), dim3(grid), dim3(256), 0, s, x, logp, force, (long long)B, p);
     PITA_LAUNCH_CHECK();
     return PITA_OK;
   }
@@ -1086,9 +1045,7 @@ extern "C" int pita_lj_logp_force(const float* x, float* logp, float* force, int
 extern "C" int pita_dw_logp_force(const float* x, float* logp, float* force, int64_t B, int n, int d, float temperature,
                                   float a, float b, float c, float d0, void* stream) {
   PITA_REQUIRE(temperature > 0.f, "pita_dw_logp_force: temperature must be > 0");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.a = a; p.b = b; p.c = c; p.d0 = d0;
-  return launch_pair<E_DW>(x, logp, force, B, n, d, p, stream);
+  return launch_pair<E_DW>(x, logp, force, B, n, d, dw_params(temperature, a, b, c, d0), stream);
 }
 
 extern "C" int pita_gmm_logp_force(const float* x, float* logp, float* force, int64_t B, int dim, const float* means,
@@ -1099,18 +1056,13 @@ extern "C" int pita_gmm_logp_force(const float* x, float* logp, float* force, in
   PITA_REQUIRE(K >= 1 && K <= 2048, "pita_gmm_logp_force: K out of range");
   PITA_REQUIRE(temperature > 0.f, "pita_gmm_logp_force: temperature must be > 0");
   if (dim < 1 || dim > 4) return fail(PITA_EUNSUPPORTED, "pita_gmm_logp_force: dim=%d (1..4 implemented)", dim);
-  if (B == 0) return PITA_OK;
-  const long long nb = (B + 255) / 256;
-  const unsigned grid = (unsigned)(nb < 4096 ? nb : 4096);
+  const unsigned grid = capped_grid((B + 255) / 256, 4096);
   const size_t lds = sizeof(float) * (size_t)(2 * K * dim + K);
   const float inv_T = 1.0f / temperature;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dim) {
-    case 1: hipLaunchKernelGGL(gmm_kernel<1>, dim3(grid), dim3(256), lds, s, x, logp, force, B, means, scales, K, inv_T); break;
-    case 2: hipLaunchKernelGGL(gmm_kernel<2>, dim3(grid), dim3(256), lds, s, x, logp, force, B, means, scales, K, inv_T); break;
-    case 3: hipLaunchKernelGGL(gmm_kernel<3>, dim3(grid), dim3(256), lds, s, x, logp, force, B, means, scales, K, inv_T); break;
-    default: hipLaunchKernelGGL(gmm_kernel<4>, dim3(grid), dim3(256), lds, s, x, logp, force, B, means, scales, K, inv_T); break;
-  }
+  dispatch_dim<4>(dim, [&](auto D) {
+    hipLaunchKernelGGL(gmm_kernel<decltype(D)::value>, dim3(grid), dim3(256), lds, (hipStream_t)stream, x, logp, force, B, means,
+                       scales, K, inv_T);
+  });
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -1128,11 +1080,7 @@ extern "C" int pita_lj_descent(float* x, const float* noise, int64_t B, int n, i
                                float noise_scale, float sqrt_dt, uint64_t seed, uint64_t walker_offset, int64_t step0,
                                int remove_mean, void* stream) {
   PITA_REQUIRE(temperature > 0.f, "pita_lj_descent: temperature must be > 0");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.energy_factor = energy_factor; p.dist_eps = dist_eps; p.eps = eps;
-  p.rm2 = rm * rm; p.osc_scale = osc_scale;
-  p.cw = -p.inv_T * (2.0f * energy_factor * eps * 12.0f / p.rm2); p.co = -p.inv_T * osc_scale;
-  return launch_descent<E_LJ>(x, noise, B, n, d, p,
+  return launch_descent<E_LJ>(x, noise, B, n, d, lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale),
                               descent_params(nsteps, dt, noise_scale, sqrt_dt, seed, walker_offset, step0, remove_mean), stream);
 }
 
@@ -1140,33 +1088,14 @@ extern "C" int pita_dw_descent(float* x, const float* noise, int64_t B, int n, i
                                float c, float d0, int nsteps, float dt, float noise_scale, float sqrt_dt, uint64_t seed,
                                uint64_t walker_offset, int64_t step0, int remove_mean, void* stream) {
   PITA_REQUIRE(temperature > 0.f, "pita_dw_descent: temperature must be > 0");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.a = a; p.b = b; p.c = c; p.d0 = d0;
-  return launch_descent<E_DW>(x, noise, B, n, d, p,
+  return launch_descent<E_DW>(x, noise, B, n, d, dw_params(temperature, a, b, c, d0),
                               descent_params(nsteps, dt, noise_scale, sqrt_dt, seed, walker_offset, step0, remove_mean), stream);
 }
 
-// one counter per step (and one spare slot that callers have always sized their buffers with)
-extern "C" size_t pita_lj_mala_workspace_bytes(int nsteps) { return 8 * (size_t)((nsteps > 0 ? nsteps : 0) + 1); }
+extern "C" size_t pita_lj_mala_workspace_bytes(int nsteps) { return mala_workspace_bytes(nsteps); }
 
-// shared frame of the fused-chain entry points: zero the per-step counters, run the chain, derive rates and final dt.
-// A non-adaptive chain is one launch; an adaptive chain is one launch per step, and the order of the stream is what lets
-// a step see the counts of the steps before it.
-template <class Launch>
-static int run_mala_chain(int nsteps, double* dt_dev, int adaptive, int64_t total, float* rates_out, void* workspace,
-                          MalaParams& q, void* stream, Launch&& launch) {
-  PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "fused MALA: workspace must be 8-byte aligned");
-  unsigned long long* sync = static_cast<unsigned long long*>(workspace);
-  PITA_HIP_CHECK(hipMemsetAsync(sync, 0, pita_lj_mala_workspace_bytes(nsteps), (hipStream_t)stream));
-  q.sync = sync;
-  q.steps = adaptive ? 1 : nsteps;
-  for (q.step_base = 0; q.step_base < nsteps; q.step_base += q.steps) {
-    const int rc = launch();
-    if (rc != PITA_OK) return rc;
-  }
-  return launch_mala_finish(dt_dev, sync, nsteps, (long long)total, adaptive, rates_out, stream);
-}
-
+// The pair-target chains (frame: run_mala_chain, pair_common.h).  With B == 0 the chain launches nothing but the finish
+// kernel still runs (rates 0, dt adapted on them): kept as it was.
 extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const float* uniforms, int64_t B, int n, int d,
                             float temperature, float energy_factor, float dist_eps, float eps, float rm, float osc_scale,
                             int nsteps, double* dt_dev, int adaptive, int64_t total, uint64_t seed,
@@ -1178,40 +1107,28 @@ extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const flo
     return fail(PITA_EUNSUPPORTED, "pita_lj_mala: fused chains exist for LJ13 and LJ55 (n = %d, d = %d)", n, d);
   if (nsteps == 0) return PITA_OK;
   PITA_REQUIRE(dt_dev && workspace && (B == 0 || (x && logp)), "pita_lj_mala: null argument");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.energy_factor = energy_factor; p.dist_eps = dist_eps; p.eps = eps;
-  p.rm2 = rm * rm; p.osc_scale = osc_scale;
-  p.cw = -p.inv_T * (2.0f * energy_factor * eps * 12.0f / p.rm2); p.co = -p.inv_T * osc_scale;
-  hipStream_t s = (hipStream_t)stream;
-  MalaParams q{};
-  q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids; q.seed = seed;
-  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev;
-  q.adaptive = adaptive; q.remove_mean = remove_mean;
+  const PairParams p = lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale);
+  MalaParams q = mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, total, dt_dev, adaptive, remove_mean,
+                             workspace);
   if (n == 55) {
-    return run_mala_chain(nsteps, dt_dev, adaptive, total, rates_out, workspace, q, stream, [&]() {
+    return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
       if (B == 0) return (int)PITA_OK;
       const int rc = ring_launch_mala(E_LJ, x, logp, B, n, d, p, q, stream);
       return rc == 1 ? fail(PITA_EUNSUPPORTED, "pita_lj_mala: no ring kernel for n = %d", n) : rc;
     });
   }
+  // one residency of the chain kernel: a performance choice (no tail wave), nothing depends on co-residency
+  int per_cu = 0, cus = 0;
+  if (int rc = resident_blocks(lj13_mala_kernel<true>, 256, 0, per_cu)) return rc;
+  if (int rc = device_cus(cus)) return rc;
   const long long nblk = (B + 127) / 128;
-  const bool unit = p.rm2 == 1.0f;
-  // one residency of the chain kernel, per device: a performance choice (no tail wave), nothing depends on co-residency
-  static PerDevice<int> capacity_on;
-  int& capacity = capacity_on.get();
-  if (capacity == 0) {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    PITA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lj13_mala_kernel<true>, 256, 0));
-    PITA_HIP_CHECK(hipGetDevice(&dev));
-    PITA_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    capacity = per_cu * prop.multiProcessorCount;
-  }
-  return run_mala_chain(nsteps, dt_dev, adaptive, total, rates_out, workspace, q, stream, [&]() {
+  const unsigned grid = capped_grid(nblk, (long long)per_cu * cus);
+  return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
     if (nblk == 0) return (int)PITA_OK;
-    const unsigned grid = (unsigned)(nblk < capacity ? nblk : capacity);
-    if (unit) hipLaunchKernelGGL(lj13_mala_kernel<true>, dim3(grid), dim3(256), 0, s, x, logp, (long long)B, p, q);
-    else hipLaunchKernelGGL(lj13_mala_kernel<false>, dim3(grid), dim3(256), 0, s, x, logp, (long long)B, p, q);
+    dispatch_bool(p.rm2 == 1.0f, [&](auto unit) {
+      hipLaunchKernelGGL(lj13_mala_kernel<decltype(unit)::value>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, logp,
+                         (long long)B, p, q);
+    });
     PITA_LAUNCH_CHECK();
     return (int)PITA_OK;
   });
@@ -1228,13 +1145,10 @@ extern "C" int pita_dw_mala(float* x, float* logp, const float* noise, const flo
     return fail(PITA_EUNSUPPORTED, "pita_dw_mala: the fused chain exists for DW4 (n = %d, d = %d)", n, d);
   if (nsteps == 0) return PITA_OK;
   PITA_REQUIRE(dt_dev && workspace && (B == 0 || (x && logp)), "pita_dw_mala: null argument");
-  PairParams p{};
-  p.inv_T = 1.0f / temperature; p.a = a; p.b = b; p.c = c; p.d0 = d0;
-  MalaParams q{};
-  q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids; q.seed = seed;
-  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev;
-  q.adaptive = adaptive; q.remove_mean = remove_mean;
-  return run_mala_chain(nsteps, dt_dev, adaptive, total, rates_out, workspace, q, stream, [&]() {
+  const PairParams p = dw_params(temperature, a, b, c, d0);
+  MalaParams q = mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, total, dt_dev, adaptive, remove_mean,
+                             workspace);
+  return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
     if (B == 0) return (int)PITA_OK;
     const int rc = ring_launch_mala(E_DW, x, logp, B, n, d, p, q, stream);
     return rc == 1 ? fail(PITA_EUNSUPPORTED, "pita_dw_mala: no ring kernel for n = %d", n) : rc;

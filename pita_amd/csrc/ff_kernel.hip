@@ -12,7 +12,9 @@
 // GPU of BASELINE config C4 put a wave on every SIMD) unless the LDS cannot hold that many (launch plan, pita_ff_create);
 // coordinates and tables live in LDS; loads and stores of x / force are contiguous spans.  ~14 kflop (+ ~60 kflop with
 // GB-OBC1) and 536 B per walker-eval for a 22-atom peptide: compute- rather than bandwidth-bound.
-#include "pair_common.h"  // launch_mala_finish (common.h comes with it)
+#include <vector>
+
+#include "pair_common.h"  // MalaParams, run_mala_chain (common.h comes with it)
 
 namespace pita {
 
@@ -395,23 +397,10 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
 // No grid-wide barrier and no wait of any kind: the only cross-block traffic is one integer atomicAdd of the accepted
 // walkers per tile and step.  A non-adaptive chain is ONE launch (tiles outside, steps inside); an adaptive chain is one
 // launch per step (stream order is the barrier), each deriving its step size from dt_dev[0] and the counts of the
-// steps before it (mala_replay_dt, pair_common.h); mala_finish_kernel (energy_kernels.hip) runs last and leaves the
-// rates and the final step size.
-struct FfMalaParams {
-  float* x;                  // [B][3 n] walkers, updated in place
-  float* logp;               // [B] log-density of x, carried
-  const float* noise;        // nullable [n_steps][B][3 n]
-  const float* uniforms;     // nullable [n_steps][B]
-  const long long* walker_ids;  // nullable [B] Philox keys of the walkers
-  unsigned long long seed, walker_offset;
-  long long step0, total, B;
-  const double* dt_dev;      // step size on entry of the CHAIN (not written by this kernel)
-  unsigned long long* sync;  // [n_steps + 1] accepted walkers per step (the layout launch_mala_finish reads)
-  int step_base, steps;      // this launch runs steps [step_base, step_base + steps) of the chain
-  int adaptive, remove_mean;
-};
-
-__global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaParams q) {
+// steps before it (mala_replay_dt); the frame around the launches is run_mala_chain (pair_common.h), shared with the
+// pair-target chains: mala_finish_kernel runs last and leaves the rates and the final step size.
+// x [B][3 n] walkers and logp [B] their log-densities, both updated in place; q as for the pair-target chains (pair_common.h).
+__global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* x, float* logp, long long B, MalaParams q) {
   extern __shared__ float sm[];
   const int n = p.n, D = 3 * n, WPB = p.wpb;
   const FfLds L = ff_stage(p, sm);
@@ -423,16 +412,16 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaP
   const double dtd = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
   const float hdt = (float)(0.5 * dtd), sdt = (float)sqrt(dtd), tdt = (float)(2.0 * dtd);
   const float sc = -p.inv_kT * p.length_scale;  // d logp / d x_model
-  const long long nblk = (q.B + WPB - 1) / WPB;
+  const long long nblk = (B + WPB - 1) / WPB;
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const long long w0 = blk * WPB;
-    const int nw = (int)((q.B - w0) < WPB ? (q.B - w0) : WPB);
-    for (int i = tid; i < nw * D; i += FF_THREADS) xu[i] = q.x[w0 * D + i];
+    const int nw = (int)((B - w0) < WPB ? (B - w0) : WPB);
+    for (int i = tid; i < nw * D; i += FF_THREADS) xu[i] = x[w0 * D + i];
     __syncthreads();
     const bool act = lane_on && wl < nw;
     const long long wg = w0 + (act ? wl : 0);
     const unsigned long long key = q.walker_ids ? (unsigned long long)q.walker_ids[wg] : q.walker_offset + (unsigned long long)wg;
-    float lp = (act && a == 0) ? q.logp[wg] : 0.f;
+    float lp = (act && a == 0) ? logp[wg] : 0.f;
     for (int st = 0; st < q.steps; ++st) {
       const int s = q.step_base + st;
       // ---- F at x
@@ -446,7 +435,7 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaP
         const float F[3] = {sc * g0, sc * g1, sc * g2};
         float xi[4] = {0.f, 0.f, 0.f, 0.f};
         if (q.noise) {
-          const long long base = (((long long)s * q.B + wg) * n + a) * 3;
+          const long long base = (((long long)s * B + wg) * n + a) * 3;
 #pragma unroll
           for (int k = 0; k < 3; ++k) xi[k] = q.noise[base + k];
         } else {
@@ -488,7 +477,7 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaP
         const float lpp = -tot * p.inv_kT;
         const float lqf = -sf / tdt, lqb = -sb / tdt;
         const float ratio = (lpp - lp) + (lqb - lqf);
-        const float u = q.uniforms ? q.uniforms[(long long)s * q.B + wg] : philox_uniform(q.seed, key, q.step0 + s, 0xFFFFFu);
+        const float u = q.uniforms ? q.uniforms[(long long)s * B + wg] : philox_uniform(q.seed, key, q.step0 + s, 0xFFFFFu);
         const float af = (logf(u) < ratio) ? 1.0f : 0.0f;
         lp = af * lpp + (1.0f - af) * lp;
         flag[wl] = af;
@@ -522,8 +511,8 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, FfMalaP
       }
       __syncthreads();
     }  // steps
-    for (int i = tid; i < nw * D; i += FF_THREADS) q.x[w0 * D + i] = xu[i];
-    if (act && a == 0) q.logp[wg] = lp;
+    for (int i = tid; i < nw * D; i += FF_THREADS) x[w0 * D + i] = xu[i];
+    if (act && a == 0) logp[wg] = lp;
     __syncthreads();
   }
 }
@@ -561,9 +550,18 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
   PITA_REQUIRE(check_idx(c->bond_idx, 2 * c->n_bonds) && check_idx(c->angle_idx, 3 * c->n_angles) &&
                    check_idx(c->tors_idx, 4 * c->n_torsions) && check_idx(c->exc_idx, 2 * c->n_exceptions),
                "pita_ff_create: atom index out of range");
+  for (int e = 0; e < c->n_exceptions; ++e)
+    PITA_REQUIRE(c->exc_idx[2 * e] != c->exc_idx[2 * e + 1], "pita_ff_create: exception with i == j");
+  const bool gb = c->gb_radius != nullptr;
+  PITA_REQUIRE(!gb || c->gb_scale, "pita_ff_create: gb_scale missing");
+  PITA_REQUIRE(!gb || (c->gb_solute_dielectric > 0.f && c->gb_solvent_dielectric > 0.f),
+               "pita_ff_create: GB dielectric constants must be > 0");
+  for (int i = 0; i < n && gb; ++i)
+    PITA_REQUIRE(c->gb_radius[i] > 0.009f, "pita_ff_create: gb_radius must exceed the 0.009 nm dielectric offset");
+  // every argument is checked: the host tables from here on are vectors, released on every way out
   // dense pair table with Lorentz-Berthelot mixing, overridden by the exceptions
-  int* pidx = new int[2 * np];
-  float* ppar = new float[4 * np];
+  std::vector<int> pidx(2 * np);
+  std::vector<float> ppar(4 * np);
   const float K = 138.935456f;
   int t = 0;
   for (int i = 0; i < n; ++i)
@@ -577,7 +575,6 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
   for (int e = 0; e < c->n_exceptions; ++e) {
     int a = c->exc_idx[2 * e], b = c->exc_idx[2 * e + 1];
     if (a > b) { int tmp = a; a = b; b = tmp; }
-    if (a == b) { delete[] pidx; delete[] ppar; return fail(PITA_EINVAL, "pita_ff_create: exception with i == j"); }
     const int tt = a * n - a * (a + 1) / 2 + (b - a - 1);
     ppar[4 * tt] = K * c->exc_par[3 * e];
     ppar[4 * tt + 1] = c->exc_par[3 * e + 1];
@@ -588,23 +585,17 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
   const size_t b_ai = sizeof(int) * 3 * c->n_angles, b_ap = sizeof(float) * 2 * c->n_angles;
   const size_t b_ti = sizeof(int) * 4 * c->n_torsions, b_tp = sizeof(float) * 3 * c->n_torsions;
   const size_t b_pi = sizeof(int) * 2 * np, b_pp = sizeof(float) * 4 * np;
-  const bool gb = c->gb_radius != nullptr;
-  PITA_REQUIRE(!gb || c->gb_scale, "pita_ff_create: gb_scale missing");
-  PITA_REQUIRE(!gb || (c->gb_solute_dielectric > 0.f && c->gb_solvent_dielectric > 0.f),
-               "pita_ff_create: GB dielectric constants must be > 0");
-  float* gpar = new float[4 * n];
+  std::vector<float> gpar(gb ? 4 * n : 0);
   for (int i = 0; i < n && gb; ++i) {
-    if (!(c->gb_radius[i] > 0.009f)) { delete[] pidx; delete[] ppar; delete[] gpar; return fail(PITA_EINVAL, "pita_ff_create: gb_radius must exceed the 0.009 nm dielectric offset"); }
     gpar[4 * i] = c->gb_radius[i] - 0.009f;
     gpar[4 * i + 1] = (c->gb_radius[i] - 0.009f) * c->gb_scale[i];
     gpar[4 * i + 2] = c->gb_radius[i];
     gpar[4 * i + 3] = c->charge[i];
   }
-  const size_t b_gb = gb ? sizeof(float) * 4 * n : 0;
+  const size_t b_gb = sizeof(float) * gpar.size();
   // per-atom interaction lists
   const int n_ent = 2 * c->n_bonds + 3 * c->n_angles + 4 * c->n_torsions;
-  int* csr_off = new int[3 * (n + 1)];
-  int* csr_ent = new int[n_ent > 0 ? n_ent : 1];
+  std::vector<int> csr_off(3 * (n + 1)), csr_ent(n_ent > 0 ? n_ent : 1);
   {
     int pos = 0;
     const int* idx[3] = {c->bond_idx, c->angle_idx, c->tors_idx};
@@ -621,7 +612,7 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
   }
   const size_t b_co = sizeof(int) * 3 * (n + 1), b_ce = sizeof(int) * (n_ent > 0 ? n_ent : 1);
   const size_t b_tc = sizeof(float) * 2 * c->n_torsions;
-  float* tcs = new float[2 * (c->n_torsions > 0 ? c->n_torsions : 1)];
+  std::vector<float> tcs(2 * c->n_torsions);
   for (int t = 0; t < c->n_torsions; ++t) {
     tcs[2 * t] = (float)cos((double)c->tors_par[3 * t + 1]);
     tcs[2 * t + 1] = (float)sin((double)c->tors_par[3 * t + 1]);
@@ -644,13 +635,11 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     lds_max = lds_optin;
   int wpb = FF_THREADS / n;
   while (wpb > 0 && blob_bytes + (size_t)wpb * walker_descent > (size_t)lds_max) --wpb;
-  if (qe != hipSuccess || wpb == 0) {
-    delete[] pidx; delete[] ppar; delete[] gpar; delete[] csr_off; delete[] csr_ent; delete[] tcs;
-    if (qe != hipSuccess) return fail(PITA_EHIP, "pita_ff_create: LDS limit query failed: %s", hipGetErrorString(qe));
+  if (qe != hipSuccess) return fail(PITA_EHIP, "pita_ff_create: LDS limit query failed: %s", hipGetErrorString(qe));
+  if (wpb == 0)
     return fail(PITA_EUNSUPPORTED,
                 "pita_ff_create: one walker needs %zu B of LDS per block (%zu B of interaction tables), the device allows %d B",
                 blob_bytes + walker_descent, blob_bytes, lds_max);
-  }
   pita_ff* ff = new pita_ff();
   ff->lds_logp = blob_bytes + (size_t)wpb * walker_logp;
   ff->lds_descent = blob_bytes + (size_t)wpb * walker_descent;
@@ -669,19 +658,13 @@ extern "C" int pita_ff_create(pita_ff_t** out, const pita_ff_config* c) {
     p.o_bond_idx = word_off(put(c->bond_idx, b_bi)); p.o_bond_par = word_off(put(c->bond_par, b_bp));
     p.o_angle_idx = word_off(put(c->angle_idx, b_ai)); p.o_angle_par = word_off(put(c->angle_par, b_ap));
     p.o_tors_idx = word_off(put(c->tors_idx, b_ti)); p.o_tors_par = word_off(put(c->tors_par, b_tp));
-    p.o_tors_cs = word_off(put(tcs, b_tc));
-    p.o_pair_idx = word_off(put(pidx, b_pi)); p.o_pair_par = word_off(put(ppar, b_pp));
-    p.o_gb_par = word_off(put(gpar, b_gb));
-    p.o_csr_off = word_off(put(csr_off, b_co)); p.o_csr_ent = word_off(put(csr_ent, b_ce));
+    p.o_tors_cs = word_off(put(tcs.data(), b_tc));
+    p.o_pair_idx = word_off(put(pidx.data(), b_pi)); p.o_pair_par = word_off(put(ppar.data(), b_pp));
+    p.o_gb_par = word_off(put(gpar.data(), b_gb));
+    p.o_csr_off = word_off(put(csr_off.data(), b_co)); p.o_csr_ent = word_off(put(csr_ent.data(), b_ce));
     p.blob = reinterpret_cast<const unsigned*>(base);
     p.blob_words = (int)(off / 4);
   }
-  delete[] pidx;
-  delete[] ppar;
-  delete[] gpar;
-  delete[] csr_off;
-  delete[] csr_ent;
-  delete[] tcs;
   if (e != hipSuccess) {
     (void)hipFree(ff->d_all);
     delete ff;
@@ -712,6 +695,9 @@ extern "C" int pita_ff_destroy(pita_ff_t* ff) {
   return PITA_OK;
 }
 
+// persistent blocks: the tables are staged once per block
+static unsigned ff_grid(const FfParams& p, int64_t B) { return capped_grid((B + p.wpb - 1) / p.wpb, kGridCus * 8); }
+
 extern "C" int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, float* force, int64_t B, void* stream) {
   PITA_REQUIRE(ff && B >= 0, "pita_ff_logp_force: bad argument");
   if (B == 0) return PITA_OK;
@@ -719,10 +705,7 @@ extern "C" int pita_ff_logp_force(pita_ff_t* ff, const float* x, float* logp, fl
   FfParams p = ff->p;
   p.x = x; p.logp = logp; p.force = force; p.B = B;
   PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_kernel<false>), ff->lds_logp));
-  const long long nblk = (B + p.wpb - 1) / p.wpb;
-  const long long cap = 256LL * 8;  // persistent blocks: the tables are staged once per block
-  hipLaunchKernelGGL(ff_kernel<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), ff->lds_logp,
-                     (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ff_kernel<false>, dim3(ff_grid(p, B)), dim3(FF_THREADS), ff->lds_logp, (hipStream_t)stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -737,15 +720,12 @@ extern "C" int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise, int6
   p.xio = x; p.noise = noise; p.B = B; p.steps = n_steps; p.dt = dt; p.noise_scale = noise_scale; p.sqrt_dt = sqrt_dt;
   p.seed = seed; p.walker_offset = walker_offset; p.step0 = step0; p.remove_mean = remove_mean;
   PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_kernel<true>), ff->lds_descent));
-  const long long nblk = (B + p.wpb - 1) / p.wpb;
-  const long long cap = 256LL * 8;
-  hipLaunchKernelGGL(ff_kernel<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(FF_THREADS), ff->lds_descent,
-                     (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ff_kernel<true>, dim3(ff_grid(p, B)), dim3(FF_THREADS), ff->lds_descent, (hipStream_t)stream, p);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
 
-extern "C" size_t pita_ff_mala_workspace_bytes(int n_steps) { return 8 * (size_t)((n_steps > 0 ? n_steps : 0) + 1); }
+extern "C" size_t pita_ff_mala_workspace_bytes(int n_steps) { return mala_workspace_bytes(n_steps); }
 
 extern "C" int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* noise, const float* uniforms, int64_t B,
                             int n_steps, double* dt_dev, int adaptive, int64_t total, uint64_t seed, uint64_t walker_offset,
@@ -754,27 +734,16 @@ extern "C" int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* n
   PITA_REQUIRE(ff && dt_dev && workspace, "pita_ff_mala: null argument (handle, dt_dev, workspace)");
   PITA_REQUIRE(B >= 0 && n_steps >= 0 && total > 0, "pita_ff_mala: bad argument (B >= 0, n_steps >= 0, total > 0)");
   PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_ff_mala: workspace must be 8-byte aligned");
-  if (B == 0 || n_steps == 0) return PITA_OK;
+  if (B == 0 || n_steps == 0) return PITA_OK;  // unlike the pair chains, an empty batch leaves dt_dev and rates_out untouched
   PITA_REQUIRE(x && logp, "pita_ff_mala: null argument (x, logp)");
-  hipStream_t s = (hipStream_t)stream;
-  FfParams p = ff->p;  // the plan of pita_ff_descent: the chain lives in the descent's LDS footprint
-  FfMalaParams q{};
-  q.x = x; q.logp = logp; q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids;
-  q.seed = seed; q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.B = B; q.dt_dev = dt_dev;
-  q.sync = static_cast<unsigned long long*>(workspace);
-  q.adaptive = adaptive ? 1 : 0; q.remove_mean = remove_mean;
-  PITA_HIP_CHECK(hipMemsetAsync(q.sync, 0, pita_ff_mala_workspace_bytes(n_steps), s));
+  const FfParams p = ff->p;  // the plan of pita_ff_descent: the chain lives in the descent's LDS footprint
+  MalaParams q = mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, total, dt_dev, adaptive, remove_mean,
+                             workspace);
   PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_mala_kernel), ff->lds_descent));
-  const long long nblk = (B + p.wpb - 1) / p.wpb;
-  const long long cap = 256LL * 8;
-  const dim3 grid((unsigned)(nblk < cap ? nblk : cap));
-  // non-adaptive: the whole chain in one launch; adaptive: one launch per step, each reads the counts of the steps before
-  const int launches = adaptive ? n_steps : 1;
-  q.steps = adaptive ? 1 : n_steps;
-  for (int l = 0; l < launches; ++l) {
-    q.step_base = l;
-    hipLaunchKernelGGL(ff_mala_kernel, grid, dim3(FF_THREADS), ff->lds_descent, s, p, q);
+  return run_mala_chain(n_steps, dt_dev, rates_out, q, stream, [&]() {
+    hipLaunchKernelGGL(ff_mala_kernel, dim3(ff_grid(p, B)), dim3(FF_THREADS), ff->lds_descent, (hipStream_t)stream, p, x, logp,
+                       (long long)B, q);
     PITA_LAUNCH_CHECK();
-  }
-  return launch_mala_finish(dt_dev, q.sync, n_steps, (long long)total, adaptive, rates_out, stream);
+    return (int)PITA_OK;
+  });
 }

@@ -33,6 +33,31 @@ struct MalaParams {
   unsigned long long* sync;  // [chain steps] walkers accepted per step, added with an integer atomic; zeroed by the wrapper
 };
 
+// The parameter blocks from the arguments of the C entry points: every pita_lj_* / pita_dw_* call builds its block here.
+// (cw / co are read by the LJ13 and ring kernels only; no E_LJS instantiation reads them.)
+inline PairParams lj_params(float temperature, float energy_factor, float dist_eps, float eps, float rm, float osc_scale) {
+  PairParams p{};
+  p.inv_T = 1.0f / temperature; p.energy_factor = energy_factor; p.dist_eps = dist_eps; p.eps = eps;
+  p.rm2 = rm * rm; p.osc_scale = osc_scale;
+  p.cw = -p.inv_T * (2.0f * energy_factor * eps * 12.0f / p.rm2); p.co = -p.inv_T * osc_scale;
+  return p;
+}
+inline PairParams dw_params(float temperature, float a, float b, float c, float d0) {
+  PairParams p{};
+  p.inv_T = 1.0f / temperature; p.a = a; p.b = b; p.c = c; p.d0 = d0;
+  return p;
+}
+// the caller's share of a chain's parameters; run_mala_chain fills in the launch's step range
+inline MalaParams mala_params(const float* noise, const float* uniforms, const int64_t* walker_ids, uint64_t seed,
+                              uint64_t walker_offset, int64_t step0, int64_t total, const double* dt_dev, int adaptive,
+                              int remove_mean, void* workspace) {
+  MalaParams q{};
+  q.noise = noise; q.uniforms = uniforms; q.walker_ids = (const long long*)walker_ids; q.seed = seed;
+  q.walker_offset = walker_offset; q.step0 = step0; q.total = total; q.dt_dev = dt_dev;
+  q.adaptive = adaptive ? 1 : 0; q.remove_mean = remove_mean; q.sync = static_cast<unsigned long long*>(workspace);
+  return q;
+}
+
 #ifdef __HIPCC__
 // Step size of chain step `step_base` of a fused chain: dt_dev[0] as the chain found it and, when adaptive,
 // mala_adapt_kernel's rule (sampler_kernels.hip; sde_integration.py:439-443) replayed over the accepted counts
@@ -54,6 +79,25 @@ __device__ __forceinline__ double mala_replay_dt(const double* dt_dev, const uns
 // rates_out[s] and the final dt from the per-step counts of a fused chain (energy_kernels.hip)
 int launch_mala_finish(double* dt_dev, const unsigned long long* sync, int nsteps, long long total, int adaptive,
                        float* rates_out, void* stream);
+
+// workspace of a fused chain: one counter per step (and one spare slot that callers have always sized their buffers with)
+inline size_t mala_workspace_bytes(int nsteps) { return 8 * (size_t)((nsteps > 0 ? nsteps : 0) + 1); }
+
+// The frame of every fused-chain entry point (pita_lj_mala, pita_dw_mala, pita_ff_mala): zero the per-step counters, run
+// the chain, derive rates and final dt.  A non-adaptive chain is one launch; an adaptive chain is one launch per step, and
+// the order of the stream is what lets a step see the counts of the steps before it.  launch() starts the kernel for the
+// step range it finds in q.
+template <class Launch>
+inline int run_mala_chain(int nsteps, double* dt_dev, float* rates_out, MalaParams& q, void* stream, Launch&& launch) {
+  PITA_REQUIRE(((uintptr_t)q.sync & 7) == 0, "fused MALA: workspace must be 8-byte aligned");
+  PITA_HIP_CHECK(hipMemsetAsync(q.sync, 0, mala_workspace_bytes(nsteps), (hipStream_t)stream));
+  q.steps = q.adaptive ? 1 : nsteps;
+  for (q.step_base = 0; q.step_base < nsteps; q.step_base += q.steps) {
+    const int rc = launch();
+    if (rc != PITA_OK) return rc;
+  }
+  return launch_mala_finish(dt_dev, q.sync, nsteps, q.total, q.adaptive, rates_out, stream);
+}
 
 // Ring kernels (ring_kernels.hip): compile-time particle count, a walker's particles on the lanes of one wavefront,
 // partner coordinates and partner forces by immediate-offset LDS reads / one cross-lane permute per pair.

@@ -514,81 +514,53 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
       __hip_atomic_fetch_add(&q.sync[t], (unsigned long long)stepcnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Persistent grids: exactly one residency of the kernel (resident blocks per CU x CUs; a performance choice -- no tail
+// wave --, nothing depends on the blocks being co-resident), or one block per four wave groups when the batch is smaller.
 template <int N, int DIM, int KIND>
 struct RingLaunch {
   using R = Ring<N, DIM>;
-  static int cus() {
-    static PerDevice<int> n_on;
-    int& n = n_on.get();
-    if (n == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-      if (n <= 0) n = 256;
-    }
-    return n;
-  }
-  static unsigned grid_for(long long B, int blocks_per_cu) {
-    const long long ngroups = (B + R::WPW - 1) / R::WPW, want = (ngroups + 3) / 4, cap = (long long)cus() * blocks_per_cu;
-    return (unsigned)(want < cap ? want : cap);
-  }
-  // resident blocks per CU of a kernel (registers and LDS decide): the persistent grids are exactly one residency
   template <class K>
-  static int resident(K kernel, size_t lds, int& cache) {
-    if (cache == 0) {
-      int v = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, 256, lds) != hipSuccess || v <= 0) v = 4;
-      cache = v;
-    }
-    return cache;
+  static int grid_for(K* kernel, size_t lds, long long B, unsigned& grid) {
+    int per_cu = 0, cus = 0;
+    if (int rc = resident_blocks(kernel, 256, lds, per_cu)) return rc;
+    if (int rc = device_cus(cus)) return rc;
+    const long long ngroups = (B + R::WPW - 1) / R::WPW;
+    grid = capped_grid((ngroups + 3) / 4, (long long)cus * per_cu);
+    return PITA_OK;
   }
+  static bool unit_rm(const PairParams& p) { return KIND == E_LJ && p.rm2 == 1.0f; }
   static int energy(const float* x, float* logp, float* force, long long B, const PairParams& p, hipStream_t s) {
     const size_t lds = sizeof(float) * 4 * R::TAB_F;
-    static PerDevice<int> occ_on[2];
-    int* occ[2] = {&occ_on[0].get(), &occ_on[1].get()};
-    if (KIND == E_LJ && p.rm2 == 1.0f) {
-      const unsigned grid = grid_for(B, resident(ring_energy_kernel<N, DIM, KIND, true>, lds, *occ[1]));
-      hipLaunchKernelGGL((ring_energy_kernel<N, DIM, KIND, true>), dim3(grid), dim3(256), lds, s, x, logp, force, B, p);
-    } else {
-      const unsigned grid = grid_for(B, resident(ring_energy_kernel<N, DIM, KIND, false>, lds, *occ[0]));
-      hipLaunchKernelGGL((ring_energy_kernel<N, DIM, KIND, false>), dim3(grid), dim3(256), lds, s, x, logp, force, B, p);
-    }
-    PITA_LAUNCH_CHECK();
-    return PITA_OK;
+    return dispatch_bool(unit_rm(p), [&](auto unit) {
+      auto* kernel = ring_energy_kernel<N, DIM, KIND, decltype(unit)::value>;
+      unsigned grid = 0;
+      if (int rc = grid_for(kernel, lds, B, grid)) return rc;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, x, logp, force, B, p);
+      PITA_LAUNCH_CHECK();
+      return (int)PITA_OK;
+    });
   }
   static int descent(float* x, const float* noise, long long B, const PairParams& p, const DescentParams& q, hipStream_t s) {
     const size_t lds = sizeof(float) * 4 * R::TAB_F;
-    static PerDevice<int> occ_on[2];
-    int* occ[2] = {&occ_on[0].get(), &occ_on[1].get()};
-    if (KIND == E_LJ && p.rm2 == 1.0f) {
-      const unsigned grid = grid_for(B, resident(ring_descent_kernel<N, DIM, KIND, true>, lds, *occ[1]));
-      hipLaunchKernelGGL((ring_descent_kernel<N, DIM, KIND, true>), dim3(grid), dim3(256), lds, s, x, noise, B, p, q);
-    } else {
-      const unsigned grid = grid_for(B, resident(ring_descent_kernel<N, DIM, KIND, false>, lds, *occ[0]));
-      hipLaunchKernelGGL((ring_descent_kernel<N, DIM, KIND, false>), dim3(grid), dim3(256), lds, s, x, noise, B, p, q);
-    }
-    PITA_LAUNCH_CHECK();
-    return PITA_OK;
+    return dispatch_bool(unit_rm(p), [&](auto unit) {
+      auto* kernel = ring_descent_kernel<N, DIM, KIND, decltype(unit)::value>;
+      unsigned grid = 0;
+      if (int rc = grid_for(kernel, lds, B, grid)) return rc;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, x, noise, B, p, q);
+      PITA_LAUNCH_CHECK();
+      return (int)PITA_OK;
+    });
   }
   static int mala(float* x, float* logp, long long B, const PairParams& p, const MalaParams& q, hipStream_t s) {
     const size_t lds = sizeof(float) * 4 * 2 * R::TAB_F;
-    const bool unit = KIND == E_LJ && p.rm2 == 1.0f;
-    // resident blocks per CU of the chain kernel, per device: the grid is one residency as a performance choice (no tail
-    // wave); nothing depends on the blocks being co-resident
-    static PerDevice<int> per_cu_on[2];
-    int& slot = per_cu_on[unit ? 1 : 0].get();
-    if (slot == 0) {
-      int v = 0;
-      if (unit) PITA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ring_mala_kernel<N, DIM, KIND, true>, 256, lds));
-      else PITA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, ring_mala_kernel<N, DIM, KIND, false>, 256, lds));
-      PITA_REQUIRE(v > 0, "ring_mala: the chain kernel does not fit a compute unit");
-      slot = v;
-    }
-    const unsigned grid = grid_for(B, slot);
-    if (unit) hipLaunchKernelGGL((ring_mala_kernel<N, DIM, KIND, true>), dim3(grid), dim3(256), lds, s, x, logp, B, p, q);
-    else hipLaunchKernelGGL((ring_mala_kernel<N, DIM, KIND, false>), dim3(grid), dim3(256), lds, s, x, logp, B, p, q);
-    PITA_LAUNCH_CHECK();
-    return PITA_OK;
+    return dispatch_bool(unit_rm(p), [&](auto unit) {
+      auto* kernel = ring_mala_kernel<N, DIM, KIND, decltype(unit)::value>;
+      unsigned grid = 0;
+      if (int rc = grid_for(kernel, lds, B, grid)) return rc;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, x, logp, B, p, q);
+      PITA_LAUNCH_CHECK();
+      return (int)PITA_OK;
+    });
   }
 };
 

@@ -8,11 +8,11 @@ reference GMM has none; the sampler never asks for it when is_molecule=False).
 """
 import torch
 
-from . import _lib
+from ._target import HipTarget
 from .base_energy_function import BaseEnergyFunction
 
 
-class GMM(BaseEnergyFunction):
+class GMM(HipTarget, BaseEnergyFunction):
     def __init__(self, dimensionality=2, n_mixes=40, loc_scaling=40, log_var_scaling=1.0, mean=None, scale=None,
                  cat_probs=None, device="cuda", should_unnormalize=False, data_normalization_factor=50,
                  temperature=1.0, **kwargs):
@@ -37,15 +37,6 @@ class GMM(BaseEnergyFunction):
                          normalization_max=data_normalization_factor)
 
     def __call__(self, samples: torch.Tensor, return_force=False):
-        x = _lib.dev_tensor(samples, "samples")
-        if self.should_unnormalize:
-            x = self.unnormalize(x)
-        x = x.reshape(-1, self._dimensionality)
-        B = x.shape[0]
-        logp = torch.empty(B, device=x.device, dtype=torch.float32)
-        force = torch.empty_like(x) if return_force else None
-        _lib.check(_lib.lib().pita_gmm_logp_force(
-            x.data_ptr(), logp.data_ptr(), _lib.ptr(force), B, self._dimensionality, self.locs.data_ptr(),
-            self.scales.data_ptr(), self.n_mixes, float(self.temperature), _lib.stream_ptr(x.device)),
-            "pita_gmm_logp_force")
-        return (logp, force) if return_force else logp
+        return self._logp_force_call("pita_gmm_logp_force", self._samples(samples, self.should_unnormalize),
+                                     self._dimensionality, self.locs.data_ptr(), self.scales.data_ptr(), self.n_mixes,
+                                     float(self.temperature), return_force=return_force)

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from ._target import PAIR_MALA_WORKSPACE, HipTarget
 from .base_energy_function import BaseMoleculeEnergy
 
 
@@ -27,7 +27,7 @@ def smooth_core_coefficients(range_min=0.65, range_max=2.0, interpolation=1000, 
     return np.ascontiguousarray(torch.tensor(c).float().numpy()[:, 0]), float(pts[0])
 
 
-class LennardJonesEnergy(BaseMoleculeEnergy):
+class LennardJonesEnergy(HipTarget, BaseMoleculeEnergy):
     def __init__(self, dimensionality, n_particles, spatial_dim, data_path=None, device="cuda",
                  plot_samples_epoch_period=5, plotting_buffer_sample_size=512, energy_factor=1.0, is_molecule=True,
                  smooth=False, temperature=1.0, should_normalize=False, data_normalization_factor=1.0,
@@ -47,56 +47,31 @@ class LennardJonesEnergy(BaseMoleculeEnergy):
         self.plot_samples_epoch_period = plot_samples_epoch_period
         self.plotting_buffer_sample_size = plotting_buffer_sample_size
 
+    def _pair_args(self):
+        """n, d, temperature, energy_factor, dist_eps, eps, rm, osc_scale of the pita_lj_* entry points."""
+        return (self.n_particles, self.n_spatial_dim, float(self.temperature), self.energy_factor, self.dist_eps, 1.0, 1.0,
+                1.0)
+
     def __call__(self, samples: torch.Tensor, return_force=False):
-        x = _lib.dev_tensor(samples, "samples")
-        if self.should_normalize:
-            x = self.unnormalize(x)
-        x = x.reshape(-1, self._dimensionality)
-        B = x.shape[0]
-        logp = torch.empty(B, device=x.device, dtype=torch.float32)
-        force = torch.empty_like(x) if return_force else None
+        x = self._samples(samples, self.should_normalize)
         if self.smooth:
-            _lib.check(_lib.lib().pita_lj_smooth_logp_force(
-                x.data_ptr(), logp.data_ptr(), _lib.ptr(force), B, self.n_particles, self.n_spatial_dim,
-                float(self.temperature), self.energy_factor, self.dist_eps, 1.0, 1.0, 1.0, self._smooth_min,
-                self._smooth_coef.ctypes.data_as(ctypes.c_void_p), _lib.stream_ptr(x.device)), "pita_lj_smooth_logp_force")
-            return (logp, force) if return_force else logp
-        _lib.check(_lib.lib().pita_lj_logp_force(
-            x.data_ptr(), logp.data_ptr(), _lib.ptr(force), B, self.n_particles, self.n_spatial_dim,
-            float(self.temperature), self.energy_factor, self.dist_eps, 1.0, 1.0, 1.0, _lib.stream_ptr(x.device)),
-            "pita_lj_logp_force")
-        return (logp, force) if return_force else logp
+            return self._logp_force_call("pita_lj_smooth_logp_force", x, *self._pair_args(), self._smooth_min,
+                                         self._smooth_coef.ctypes.data_as(ctypes.c_void_p), return_force=return_force)
+        return self._logp_force_call("pita_lj_logp_force", x, *self._pair_args(), return_force=return_force)
 
     def fused_descent(self, x, num_steps, dt, noise_scale, sqrt_dt, seed=0, walker_offset=0, step0=0, remove_mean=True,
                       noise=None):
-        """``num_steps`` of x <- remove_mean(x + F dt + noise_scale*sqrt_dt*xi) in ONE launch, in place
-        (negative_time_descent, sde_integration.py:353-360); None when the fused kernel does not apply."""
+        """The fused descent of the table in _target.py (pita_lj_descent; negative_time_descent, sde_integration.py:353-360)."""
         if self.should_normalize or self.smooth:  # the fused kernels know the plain LJ curve only
             return None
-        _lib.check(_lib.lib().pita_lj_descent(
-            x.data_ptr(), _lib.ptr(noise), x.shape[0], self.n_particles, self.n_spatial_dim, float(self.temperature),
-            self.energy_factor, self.dist_eps, 1.0, 1.0, 1.0, int(num_steps), float(dt), float(noise_scale),
-            float(sqrt_dt), seed, walker_offset, step0, int(remove_mean), _lib.stream_ptr(x.device)), "pita_lj_descent")
-        return x
+        return self._descent_call("pita_lj_descent", x, noise, self._pair_args(), num_steps, dt, noise_scale, sqrt_dt, seed,
+                                  walker_offset, step0, remove_mean)
 
     def fused_mala(self, x, logp, num_steps, dt_dev, adaptive, total, noise=None, uniforms=None, seed=0, walker_offset=0,
                    walker_ids=None, step0=0, remove_mean=True, rates_out=None):
-        """All ``num_steps`` MALA steps in fused launches, in place on ``x`` / ``logp`` / ``dt_dev`` (pita_lj_mala;
-        metropolis_hastings_mala(_adaptive), sde_integration.py:362-470): one launch for a non-adaptive chain, one per
-        step for an adaptive one.  Returns None when the fused kernel does not apply (other particle numbers, normalised
-        coordinates): the caller then runs the launch-per-kernel path, which gives the same bits.  LJ13 and LJ55 have
-        fused chains."""
+        """The fused MALA chain of the table in _target.py (pita_lj_mala; metropolis_hastings_mala(_adaptive),
+        sde_integration.py:362-470).  LJ13 and LJ55 have fused chains, on plain (not normalised, not smooth) coordinates."""
         if self.should_normalize or self.smooth or self.n_particles not in (13, 55) or self.n_spatial_dim != 3:
             return None
-        L = _lib.lib()
-        ws = torch.empty((int(L.pita_lj_mala_workspace_bytes(int(num_steps))) + 7) // 8, device=x.device, dtype=torch.int64)
-        rc = L.pita_lj_mala(x.data_ptr(), logp.data_ptr(), _lib.ptr(noise), _lib.ptr(uniforms), x.shape[0],
-                            self.n_particles, 3,
-                            float(self.temperature), self.energy_factor, self.dist_eps, 1.0, 1.0, 1.0, int(num_steps),
-                            dt_dev.data_ptr(), int(bool(adaptive)), int(total), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                            int(walker_offset), _lib.ptr(walker_ids), int(step0), int(bool(remove_mean)),
-                            _lib.ptr(rates_out), ws.data_ptr(), _lib.stream_ptr(x.device))
-        if rc == -2:  # PITA_EUNSUPPORTED
-            return None
-        _lib.check(rc, "pita_lj_mala")
-        return x
+        return self._mala_call("pita_lj_mala", PAIR_MALA_WORKSPACE, x, logp, self._pair_args(), num_steps, dt_dev, adaptive,
+                               total, noise, uniforms, seed, walker_offset, walker_ids, step0, remove_mean, rates_out)

@@ -87,6 +87,27 @@ int main(void) {
   fc.n_atoms = -1;
   rc = pita_ff_create(&ff, &fc);
   EXPECT(rc == PITA_EINVAL, 62);
+  /* generalised-Born arguments are refused from the arguments alone, with nothing allocated on the way (LeakSanitizer):
+     a radius table without its scale table, and a dielectric constant that is not positive */
+  float gr[3] = {0.15f, 0.12f, 0.17f}, gs[3] = {0.8f, 0.85f, 0.72f};
+  fc.n_atoms = 2; fc.gb_radius = gr; fc.gb_scale = NULL; fc.gb_solute_dielectric = 1.0f; fc.gb_solvent_dielectric = 78.5f;
+  ff = NULL;
+  rc = pita_ff_create(&ff, &fc);
+  EXPECT(rc == PITA_EINVAL && ff == NULL, 63);
+  fc.gb_scale = gs; fc.gb_solvent_dielectric = 0.0f;
+  rc = pita_ff_create(&ff, &fc);
+  EXPECT(rc == PITA_EINVAL && ff == NULL, 64);
+  /* a valid 3-atom configuration (two bonds, one angle, GB on): created and destroyed with a GPU, released without one */
+  int b3[4] = {0, 1, 1, 2}, a3[3] = {0, 1, 2};
+  float bp3[4] = {0.1f, 100.0f, 0.11f, 120.0f}, ap3[2] = {1.9f, 50.0f};
+  float q3[3] = {0.2f, -0.4f, 0.2f}, sg3[3] = {0.3f, 0.32f, 0.3f}, ep3[3] = {0.1f, 0.2f, 0.1f};
+  memset(&fc, 0, sizeof fc);
+  fc.n_atoms = 3; fc.n_bonds = 2; fc.bond_idx = b3; fc.bond_par = bp3; fc.n_angles = 1; fc.angle_idx = a3; fc.angle_par = ap3;
+  fc.charge = q3; fc.sigma = sg3; fc.epsilon = ep3; fc.length_scale = 1.0f; fc.kT = 2.5f;
+  fc.gb_radius = gr; fc.gb_scale = gs; fc.gb_solute_dielectric = 1.0f; fc.gb_solvent_dielectric = 78.5f;
+  fc.gb_surface_area_factor = 28.3919551f;
+  rc = pita_ff_create(&ff, &fc);
+  if (rc == PITA_OK) { rc = pita_ff_destroy(ff); EXPECT(rc == PITA_OK, 65); } else { EXPECT(ff == NULL, 66); }
   free(buf); free(w); free(ww); free(h0); free(mw);
   printf("sanitized abi ok\n");
   return 0;

@@ -247,6 +247,38 @@ def test_gmm_golden(pa, golden):
     np.testing.assert_allclose(grad.cpu().numpy(), g["grad_T1.0"], rtol=3e-5, atol=2e-5)
 
 
+def _guarded_targets(pa):
+    """(target, x [17, D] on cuda:0) of the three classes that took the device guard with the HipTarget mix-in."""
+    gen = torch.Generator().manual_seed(17)
+    lj = torch.tensor(np.load(os.path.join(ROOT, "tests", "golden", "lj13_logp_force.npz"))["x"][:17])
+    return [(pa.LennardJonesEnergy(39, 13, 3), lj.float().cuda(0)),
+            (pa.MultiDoubleWellEnergy(), (torch.randn(17, 8, generator=gen) * 2.5).cuda(0)),
+            (pa.GMM(device="cuda:0"), ((torch.rand(17, 2, generator=gen) - 0.5) * 90).cuda(0))]
+
+
+def test_targets_under_device_guard_equal_bare_calls(pa):
+    """__call__ of LennardJonesEnergy, MultiDoubleWellEnergy and GMM under ``torch.cuda.device(x.device)`` gives the bits
+    of the bare call (with one device nothing else is observable), B = 17."""
+    for e, x in _guarded_targets(pa):
+        lp, f = e(x, return_force=True)
+        with torch.cuda.device(x.device):
+            lp_g, f_g = e(x, return_force=True)
+        assert torch.isfinite(lp).all() and torch.isfinite(f).all(), type(e).__name__
+        assert torch.equal(lp, lp_g) and torch.equal(f, f_g), type(e).__name__
+
+
+def test_targets_follow_the_tensors_device_not_the_current_one(pa):
+    """With another device current, a target evaluates on its tensor's device: same bits, outputs on that device."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices: with one, the current device is always the tensor's")
+    for e, x in _guarded_targets(pa):
+        lp, f = e(x, return_force=True)
+        with torch.cuda.device(1):
+            lp_o, f_o = e(x, return_force=True)
+        assert lp_o.device == x.device and f_o.device == x.device
+        assert torch.equal(lp, lp_o) and torch.equal(f, f_o), type(e).__name__
+
+
 # ------------------------------------------------------------------------------- EGNN
 def make_net(pa, n, d, weights, temp=True, **kw):
     if temp:
