@@ -759,6 +759,44 @@ int pita_pair_distance_histogram(const float* x, const float* logw /*nullable*/,
 int pita_weighted_moments(const float* v, const float* logw /*nullable*/, int64_t n_pop, int64_t pop_size, double* out,
                           void* stream);
 
+/* ---------------------------------------------------------------- dihedral angles and weighted Ramachandran maps
+ * An extension: the reference takes (phi, psi) from mdtraj on the host, unweighted, the batch as one population.
+ *
+ * x: device float [B, n_atoms * 3], 3-D coordinates, 4 <= n_atoms <= 256 (the force field's limit).  A quad is four
+ * atoms (i, j, k, l); its angle is the torsion of pita_ff_logp_force, formula and sign, in fp32 without contraction, every
+ * operation rounded on its own, so that a numpy float32 restatement differs only by atan2f's last ulps:
+ *   b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k;  n1 = b1 x b2, n2 = b2 x b3 (a_y b_z - a_z b_y, ...);
+ *   y = (b1 . n2) * sqrt(b2 . b2), the root correctly rounded;  xv = n1 . n2;  dots as ((p0 + p1) + p2);
+ *   theta = atan2f(y, xv) in [-pi, pi].
+ * Collinear atoms give atan2f of two zeros, which is 0 (pi where xv is -0): a value like any other, counted like any
+ * other.  Where y or xv is not finite -- a non-finite coordinate among the four atoms, or products beyond the fp32
+ * range -- the angle is NaN.
+ * quads live on the DEVICE (int32), so the entry points cannot check them without a copy: the CALLER guarantees
+ * 0 <= index < n_atoms (four distinct atoms for a meaningful angle); pita_amd.metrics checks before it uploads.
+ * All argument checks run before any device call.  Both kernels stage chunks of walker rows in LDS with coalesced reads.
+ *
+ * pita_dihedral_angles: out float [B, n_dih], out[b, k] = angle of quad k (quads int32 [n_dih, 4]) of walker b;
+ * 1 <= n_dih <= 1024; B = 0 is a no-op. */
+int pita_dihedral_angles(const float* x, int64_t B, int n_atoms, const int32_t* quads, int n_dih, float* out, void* stream);
+/* Importance-weighted 2-D histograms of angle pairs per population, from the coordinates, no angle in memory.
+ * quads int32 [n_pair, 2, 4]: the a-quad and the b-quad of every pair (phi and psi of a residue), 1 <= n_pair <= 64.
+ * Each angle is binned on its own axis by the rule of pita_histogram (the same device function): edges_a / edges_b
+ * device float [nbins_a + 1] / [nbins_b + 1], ascending, the last bin closed -- +pi falls into the last bin, there is
+ * no wrap-around.  A walker is left out of a pair's cells when either angle is NaN or outside its edges.
+ * Populations, logw, m_p, the left-out walkers and the fixed-point sums are those of pita_weighted_histogram with
+ * shift = min(40, 62 - ceil(log2(pop_size))) (one value per walker and cell array); a block works on one (population,
+ * pair) with LDS-privatised 64-bit cells and ends with one 64-bit integer add per non-empty cell, so the output bits
+ * depend neither on the order of the walkers, nor on n_pop, nor on p, nor on the run.
+ *  wsum   uint64 [n_pop, n_pair, nbins_a, nbins_b]  the fixed-point sums; the weighted histogram is wsum * 2^-shift
+ *  counts uint64 [n_pop, n_pair, nbins_a, nbins_b]  plain counts over the walkers that were not left out
+ *  info   double [n_pop, 4]                         {m_p, n_bad, n_neg_inf, shift}
+ * nbins_a, nbins_b >= 1; nbins_a * nbins_b <= 4096 (64 x 64: the sums and counts of a block are then 64 KB of the
+ * 160 KB of LDS), a larger product is PITA_EUNSUPPORTED, as is shift < 20.  Outputs are overwritten. */
+int pita_dihedral_histogram2d(const float* x, const float* logw /*nullable*/, int64_t n_pop, int64_t pop_size, int n_atoms,
+                              const int32_t* quads, int n_pair, const float* edges_a, int nbins_a, const float* edges_b,
+                              int nbins_b, unsigned long long* wsum, unsigned long long* counts, double* info,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // The bin rule shared by every histogram kernel of the library (pita_histogram, pita_weighted_histogram,
-// pita_pair_distance_histogram): numpy.histogram's.
+// pita_pair_distance_histogram, pita_dihedral_histogram2d per axis): numpy.histogram's.
 #pragma once
 #include "common.h"
 

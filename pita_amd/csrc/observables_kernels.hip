@@ -278,6 +278,124 @@ __global__ void __launch_bounds__(OBS_ST) weighted_moments_kernel(const float* _
   }
 }
 
+// ---- dihedral angles (pita_hip.h: pita_dihedral_angles, pita_dihedral_histogram2d)
+constexpr int DIH_ANGLE_W = 64, DIH_ANGLE_FLOATS = 4096;  // walkers / coordinates an angle block stages at most
+constexpr int DIH_HIST_W = OBS_T, DIH_HIST_FLOATS = 8192;  // the same for a 2-D histogram block: one walker per thread
+constexpr int DIH_MAX_DIH = 1024, DIH_MAX_PAIRS = 64, DIH_MAX_CELLS = 4096, DIH_MAX_ATOMS = 256;
+constexpr int DIH_GRID = 512;  // blocks a 2-D histogram launch aims at: each clears and flushes up to 2 * 4096 cells
+
+__device__ __forceinline__ float dih_dot(const float (&a)[3], const float (&b)[3]) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2]));
+}
+__device__ __forceinline__ void dih_cross(float (&n)[3], const float (&a)[3], const float (&b)[3]) {
+  n[0] = __fsub_rn(__fmul_rn(a[1], b[2]), __fmul_rn(a[2], b[1]));
+  n[1] = __fsub_rn(__fmul_rn(a[2], b[0]), __fmul_rn(a[0], b[2]));
+  n[2] = __fsub_rn(__fmul_rn(a[0], b[1]), __fmul_rn(a[1], b[0]));
+}
+// Torsion angle in [-pi, pi] of the atoms q[0 .. 3] = (i, j, k, l) of one walker, r = its 3-D coordinates: the force
+// field's formula and sign (ff_kernel.hip), in fp32 with every operation rounded on its own, in this order:
+//   b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k;  n1 = b1 x b2, n2 = b2 x b3;
+//   y = (b1 . n2) * sqrt(b2 . b2) (the root correctly rounded), xv = n1 . n2, dots as ((p0 + p1) + p2);  atan2f(y, xv).
+// Collinear atoms give atan2f of two zeros, 0 (pi where xv is -0), a value like any other; NaN where y or xv is not
+// finite (a non-finite coordinate among the four atoms, or products beyond the fp32 range).
+__device__ __forceinline__ float dihedral_angle(const float* r, const int* q) {
+  const float *xi = r + 3 * q[0], *xj = r + 3 * q[1], *xk = r + 3 * q[2], *xl = r + 3 * q[3];
+  float b1[3], b2[3], b3[3], n1[3], n2[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    b1[c] = __fsub_rn(xj[c], xi[c]);
+    b2[c] = __fsub_rn(xk[c], xj[c]);
+    b3[c] = __fsub_rn(xl[c], xk[c]);
+  }
+  dih_cross(n1, b1, b2);
+  dih_cross(n2, b2, b3);
+  const float y = __fmul_rn(dih_dot(b1, n2), (float)sqrt((double)dih_dot(b2, b2)));
+  const float xv = dih_dot(n1, n2);
+  if (!(fabsf(y) < INFINITY && fabsf(xv) < INFINITY)) return __uint_as_float(0x7fc00000u);
+  return atan2f(y, xv);
+}
+
+// Block b takes the chunks b, b + gridDim.x, ... of W walkers: their rows are staged in LDS by coalesced reads (a
+// thread that gathered its twelve floats from global memory would use a fraction of every line), then the threads
+// stride over the (walker, dihedral) items, so that the stores are coalesced too.
+__global__ void __launch_bounds__(OBS_T) dihedral_angles_kernel(const float* __restrict__ x, long long B, int D,
+                                                                const int* __restrict__ quads, int n_dih, int W,
+                                                                float* __restrict__ out) {
+  extern __shared__ unsigned long long obs_lds[];  // [n_dih * 4] atoms | [W * D] coordinates
+  int* qd = reinterpret_cast<int*>(obs_lds);
+  float* xs = reinterpret_cast<float*>(qd + 4 * n_dih);
+  for (int i = threadIdx.x; i < 4 * n_dih; i += OBS_T) qd[i] = quads[i];
+  const long long chunks = (B + W - 1) / W;
+  for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const long long w0 = c * W;
+    const int nw = (int)(B - w0 < W ? B - w0 : W);
+    __syncthreads();  // the previous chunk has been consumed (first pass: the atoms are in place)
+    const float* src = x + w0 * D;
+    for (int i = threadIdx.x; i < nw * D; i += OBS_T) xs[i] = src[i];
+    __syncthreads();
+    float* dst = out + w0 * n_dih;
+    const unsigned items = (unsigned)(nw * n_dih);
+    for (unsigned it = threadIdx.x; it < items; it += OBS_T) {
+      const unsigned w = it / (unsigned)n_dih, k = it - w * (unsigned)n_dih;
+      dst[it] = dihedral_angle(xs + w * (unsigned)D, qd + 4 * k);
+    }
+  }
+}
+
+// Block blockIdx.x = (p * n_pair + pr) * bpp + b: pair pr of population p, the chunks b, b + bpp, ... of W walkers.  The
+// rows of a chunk and its fixed-point weights are staged as above; thread t takes walker t of the chunk, computes the two
+// angles of the pair (never written to memory), bins each on its own axis and adds to cell ia * nb + ib.
+__global__ void __launch_bounds__(OBS_T) dihedral_histogram2d_kernel(const float* __restrict__ x, const float* __restrict__ logw,
+                                                                     long long S, int D, const int* __restrict__ quads,
+                                                                     int n_pair, int W, int bpp,
+                                                                     const float* __restrict__ edges_a, int na,
+                                                                     const float* __restrict__ edges_b, int nb, int shift,
+                                                                     const unsigned long long* __restrict__ info,
+                                                                     unsigned long long* __restrict__ wsum,
+                                                                     unsigned long long* __restrict__ counts) {
+  extern __shared__ unsigned long long obs_lds[];  // cells | [W] q | [na + 1], [nb + 1] edges | [W * D] coordinates
+  const int ncell = na * nb, ncopy = obs_ncopy(ncell);
+  unsigned long long* qs = obs_lds + 2 * ncopy * ncell;
+  float* ea = reinterpret_cast<float*>(qs + W);
+  float* eb = ea + na + 1;
+  float* xs = eb + nb + 1;
+  obs_bins_clear(obs_lds, ncell, ncopy);
+  for (int i = threadIdx.x; i <= na; i += OBS_T) ea[i] = edges_a[i];
+  for (int i = threadIdx.x; i <= nb; i += OBS_T) eb[i] = edges_b[i];
+  __syncthreads();
+  const long long g = blockIdx.x / bpp, b = blockIdx.x % bpp;  // g = p * n_pair + pr: the cell array of the block
+  const long long p = g / n_pair;
+  const int* q8 = quads + 8 * (g % n_pair);
+  int qa[4], qb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { qa[k] = q8[k]; qb[k] = q8[4 + k]; }
+  const float* lw = logw ? logw + p * S : nullptr;
+  const double m = obs_key_max(info[4 * p]);
+  const float lo_a = ea[0], hi_a = ea[na], inv_a = (float)na / (hi_a - lo_a);
+  const float lo_b = eb[0], hi_b = eb[nb], inv_b = (float)nb / (hi_b - lo_b);
+  const long long chunks = (S + W - 1) / W;
+  for (long long c = b; c < chunks; c += bpp) {
+    const long long w0 = c * W;
+    const int nw = (int)(S - w0 < W ? S - w0 : W);
+    __syncthreads();  // the previous chunk has been consumed
+    const float* src = x + (p * S + w0) * D;
+    for (int i = threadIdx.x; i < nw * D; i += OBS_T) xs[i] = src[i];
+    for (int i = threadIdx.x; i < nw; i += OBS_T) qs[i] = obs_weight_q(lw, w0 + i, m, shift);
+    __syncthreads();
+    for (int w = threadIdx.x; w < nw; w += OBS_T) {
+      const unsigned long long q = qs[w];
+      if (q == OBS_LEFT_OUT) continue;
+      const float* r = xs + w * D;
+      const int ia = hist_bin(dihedral_angle(r, qa), ea, na, lo_a, hi_a, inv_a);
+      if (ia < 0) continue;
+      const int ib = hist_bin(dihedral_angle(r, qb), eb, nb, lo_b, hi_b, inv_b);
+      if (ib >= 0) obs_bins_add(obs_lds, ncell, ncopy, ia * nb + ib, q);
+    }
+  }
+  __syncthreads();
+  obs_bins_flush(obs_lds, ncell, ncopy, wsum + g * ncell, counts + g * ncell);
+}
+
 // shift = min(40, 62 - ceil(log2(pop_size * values_per_walker))), or -1 where that is below 20 (the product above 2^42)
 int obs_shift(int64_t pop_size, int64_t values_per_walker) {
   const int64_t cap = (int64_t)1 << (62 - OBS_MIN_SHIFT);
@@ -394,4 +512,64 @@ extern "C" int pita_weighted_moments(const float* v, const float* logw, int64_t 
                      (long long)pop_size, out);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
+}
+
+extern "C" int pita_dihedral_angles(const float* x, int64_t B, int n_atoms, const int32_t* quads, int n_dih, float* out,
+                                    void* stream) {
+  PITA_REQUIRE(quads && B >= 0 && (B == 0 || (x && out)), "pita_dihedral_angles: null x, quads or out, or B = %lld < 0",
+               (long long)B);
+  PITA_REQUIRE(n_atoms >= 4 && n_atoms <= DIH_MAX_ATOMS && n_dih >= 1 && n_dih <= DIH_MAX_DIH,
+               "pita_dihedral_angles: 4 <= n_atoms <= %d and 1 <= n_dih <= %d (got %d, %d)", DIH_MAX_ATOMS, DIH_MAX_DIH,
+               n_atoms, n_dih);
+  const int D = 3 * n_atoms;
+  OBS_REQUIRE_SUPPORTED(B <= INT64_MAX / (D > n_dih ? D : n_dih), "pita_dihedral_angles: B = %lld is too large", (long long)B);
+  if (B == 0) return PITA_OK;
+  int W = DIH_ANGLE_FLOATS / D < DIH_ANGLE_W ? DIH_ANGLE_FLOATS / D : DIH_ANGLE_W;  // >= 5: D <= 768
+  if (B < W) W = (int)B;
+  const size_t lds = sizeof(int) * 4 * (size_t)n_dih + sizeof(float) * (size_t)W * D;
+  hipLaunchKernelGGL(dihedral_angles_kernel, dim3(capped_grid((B + W - 1) / W, kGridCus * 8)), dim3(OBS_T), lds,
+                     (hipStream_t)stream, x, (long long)B, D, quads, n_dih, W, out);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+extern "C" int pita_dihedral_histogram2d(const float* x, const float* logw, int64_t n_pop, int64_t pop_size, int n_atoms,
+                                         const int32_t* quads, int n_pair, const float* edges_a, int nbins_a,
+                                         const float* edges_b, int nbins_b, unsigned long long* wsum,
+                                         unsigned long long* counts, double* info, void* stream) {
+  PITA_REQUIRE(x && quads && edges_a && edges_b && wsum && counts && info,
+               "pita_dihedral_histogram2d: null x, quads, edges_a, edges_b, wsum, counts or info");
+  PITA_REQUIRE(n_pop >= 1 && pop_size >= 1, "pita_dihedral_histogram2d: n_pop and pop_size must be >= 1 (got %lld, %lld)",
+               (long long)n_pop, (long long)pop_size);
+  PITA_REQUIRE(n_atoms >= 4 && n_atoms <= DIH_MAX_ATOMS && n_pair >= 1 && n_pair <= DIH_MAX_PAIRS,
+               "pita_dihedral_histogram2d: 4 <= n_atoms <= %d and 1 <= n_pair <= %d (got %d, %d)", DIH_MAX_ATOMS,
+               DIH_MAX_PAIRS, n_atoms, n_pair);
+  PITA_REQUIRE(nbins_a >= 1 && nbins_b >= 1, "pita_dihedral_histogram2d: nbins_a and nbins_b must be >= 1 (got %d, %d)",
+               nbins_a, nbins_b);
+  OBS_REQUIRE_SUPPORTED((int64_t)nbins_a * nbins_b <= DIH_MAX_CELLS,
+                        "pita_dihedral_histogram2d: nbins_a * nbins_b = %d * %d is above the limit of %d cells (64 x 64: a "
+                        "block keeps the sums and counts of its cells in LDS)", nbins_a, nbins_b, DIH_MAX_CELLS);
+  const int shift = obs_shift(pop_size, 1);
+  OBS_REQUIRE_SUPPORTED(shift >= OBS_MIN_SHIFT, "pita_dihedral_histogram2d: pop_size = %lld leaves a fixed-point shift below %d",
+                        (long long)pop_size, OBS_MIN_SHIFT);
+  const int D = 3 * n_atoms, ncell = nbins_a * nbins_b;
+  int W = DIH_HIST_FLOATS / D < DIH_HIST_W ? DIH_HIST_FLOATS / D : DIH_HIST_W;  // >= 10: D <= 768
+  if (pop_size < W) W = (int)pop_size;
+  const int64_t groups_max = INT_MAX / ((int64_t)n_pair * ncell);  // the cell arrays of all populations: an int for obs_prepare
+  OBS_REQUIRE_SUPPORTED(n_pop <= groups_max && n_pop <= INT64_MAX / pop_size / D,
+                        "pita_dihedral_histogram2d: n_pop = %lld is too large", (long long)n_pop);
+  const int64_t groups = n_pop * n_pair;
+  const int bpp = obs_blocks_per_pop(groups, (pop_size + W - 1) / W, DIH_GRID);
+  OBS_REQUIRE_SUPPORTED(groups <= INT_MAX / bpp, "pita_dihedral_histogram2d: n_pop = %lld is too large", (long long)n_pop);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t lds = sizeof(unsigned long long) * (2 * obs_ncopy(ncell) * (size_t)ncell + (size_t)W) +
+                     sizeof(float) * ((size_t)nbins_a + nbins_b + 2 + (size_t)W * D);
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(dihedral_histogram2d_kernel), lds));
+  const int rc = obs_prepare(logw, n_pop, pop_size, n_pair * ncell, wsum, counts, info, s);
+  if (rc != PITA_OK) return rc;
+  hipLaunchKernelGGL(dihedral_histogram2d_kernel, dim3((unsigned)(groups * bpp)), dim3(OBS_T), lds, s, x, logw,
+                     (long long)pop_size, D, quads, n_pair, W, bpp, edges_a, nbins_a, edges_b, nbins_b, shift,
+                     reinterpret_cast<const unsigned long long*>(info), wsum, counts);
+  PITA_LAUNCH_CHECK();
+  return obs_finish(info, n_pop, shift, s);
 }

@@ -299,3 +299,166 @@ def sample_histograms(energy_function, samples: torch.Tensor, test_set: torch.Te
             "dist_samples": _density(histogram(d_gen, d_edges), d_edges),
             "energy_edges": e_edges, "energy_test": _density(histogram(e_test, e_edges), e_edges),
             "energy_samples": _density(histogram(e_gen, e_edges), e_edges)}
+
+
+# ------------------------------------------------------------------------------------------------- dihedral observables
+# An extension: the reference takes (phi, psi) from mdtraj on the host, unweighted, the batch as one population.
+ALDP_PHI_PSI = ((4, 6, 8, 14), (6, 8, 14, 16))  # alanine dipeptide in amber order: phi = (C, N, CA, C), psi = (N, CA, C, N)
+
+
+def _residues(atom_names, residue_index):
+    names, res = list(atom_names), [int(r) for r in residue_index]
+    if len(names) != len(res):
+        raise ValueError(f"{len(names)} atom names for {len(res)} residue indices")
+    atoms = {}
+    for i, (nm, r) in enumerate(zip(names, res)):
+        atoms.setdefault(r, {}).setdefault(nm, i)
+    return atoms
+
+
+def phi_psi_quads(atom_names, residue_index):
+    """Backbone dihedrals from a topology: for every residue r with backbone atoms N, CA, C whose neighbours r - 1 and
+    r + 1 exist and carry a C and an N, phi = (C of r - 1, N, CA, C) and psi = (N, CA, C, N of r + 1).  ``atom_names`` /
+    ``residue_index``: one name and one residue number per atom, in the order of the coordinates.  Returns
+    ``(quads, residues)``: int64 numpy ``[n_res, 2, 4]`` (what ``ramachandran_histogram`` takes) and the residue numbers."""
+    import numpy as np
+
+    atoms = _residues(atom_names, residue_index)
+    quads, residues = [], []
+    for r in sorted(atoms):
+        a, prev, nxt = atoms[r], atoms.get(r - 1, {}), atoms.get(r + 1, {})
+        if all(k in a for k in ("N", "CA", "C")) and "C" in prev and "N" in nxt:
+            quads.append(((prev["C"], a["N"], a["CA"], a["C"]), (a["N"], a["CA"], a["C"], nxt["N"])))
+            residues.append(r)
+    return np.array(quads, dtype=np.int64).reshape(-1, 2, 4), np.array(residues, dtype=np.int64)
+
+
+def chirality_quads(atom_names, residue_index):
+    """``(CA, N, C, CB)`` for every residue that has these four atoms: int64 numpy ``[n_centres, 4]`` and the residue
+    numbers.  With b1 = N - CA, b2 = C - N, b3 = CB - C the numerator of that dihedral is y = (b1 . (b2 x b3)) |b2|, and
+    b1 . (b2 x b3) = (N - CA) . ((C - CA) x (CB - CA)): the sign of the angle's sine is the handedness of the centre."""
+    import numpy as np
+
+    atoms = _residues(atom_names, residue_index)
+    rows = [(r, a) for r, a in sorted(atoms.items()) if all(k in a for k in ("CA", "N", "C", "CB"))]
+    return (np.array([(a["CA"], a["N"], a["C"], a["CB"]) for _, a in rows], dtype=np.int64).reshape(-1, 4),
+            np.array([r for r, _ in rows], dtype=np.int64))
+
+
+def _dihedral_args(samples, quads, width, energy_function):
+    """Host-side checks first, then the device tensors: ``samples`` [B, n * 3] or [B, n, 3] as float32 [B, n * 3]
+    (unnormalised as ``pair_distance_histogram`` does when the target normalises), n, and ``quads`` (trailing shape
+    ``width``, or one item of it) as int32 on the samples' device.  The index check is the one the C entry points leave to
+    their caller: every index in [0, n) and the four atoms of a quad distinct."""
+    import numpy as np
+    from . import _lib
+
+    if samples.dim() not in (2, 3) or (samples.dim() == 3 and samples.shape[-1] != 3) or samples.shape[-1] % 3:
+        raise ValueError(f"samples: expected [B, n * 3] or [B, n, 3], got {tuple(samples.shape)}")
+    n = samples.shape[1] if samples.dim() == 3 else samples.shape[1] // 3
+    x = samples.reshape(samples.shape[0], 3 * n)  # (an empty batch keeps its width)
+    q = np.asarray(quads)
+    if q.ndim == len(width):
+        q = q[None]
+    if q.ndim != len(width) + 1 or q.shape[1:] != width or q.shape[0] < 1 or q.dtype.kind not in "iu":
+        raise ValueError(f"quads: expected integers of shape [k, {', '.join(map(str, width))}], got {q.dtype} {q.shape}")
+    if q.min() < 0 or q.max() >= n:
+        raise ValueError(f"quads: atom indices must be in [0, {n}), got {int(q.min())} .. {int(q.max())}")
+    flat = np.sort(q.reshape(-1, 4), axis=1)
+    if (flat[:, 1:] == flat[:, :-1]).any():
+        raise ValueError("quads: the four atoms of a dihedral must be distinct")
+    if energy_function is not None and energy_function.should_normalize:
+        x = energy_function.unnormalize(x)
+    x = _lib.dev_tensor(x, "samples")
+    return x, n, torch.from_numpy(np.ascontiguousarray(q, dtype=np.int32)).to(x.device)
+
+
+def dihedral_angles(samples: torch.Tensor, quads, energy_function=None) -> torch.Tensor:
+    """Dihedral angles in [-pi, pi] of the atom quadruples ``quads`` ([n_dih, 4] or one quad) of every walker
+    (pita_dihedral_angles; the force field's torsion, formula and sign, in fp32).  ``samples``: device tensor [B, n * 3] or
+    [B, n, 3]; ``energy_function`` (optional): a target whose ``should_normalize`` is set unnormalises the samples first.
+    Returns float32 [B, n_dih] on the device; NaN where a coordinate of the quad is not finite."""
+    from . import _lib
+
+    x, n, q = _dihedral_args(samples, quads, (4,), energy_function)
+    out = torch.empty(x.shape[0], q.shape[0], dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().pita_dihedral_angles(_lib.ptr(x), x.shape[0], n, q.data_ptr(), q.shape[0], _lib.ptr(out),
+                                               _lib.stream_ptr(x.device)), "pita_dihedral_angles")
+    return out
+
+
+def chirality_fraction(samples: torch.Tensor, quads, logweights: torch.Tensor = None, populations: int = 1):
+    """Weighted fraction of walkers whose ``chirality_quads`` dihedral (CA, N, C, CB) has a positive sine, i.e. whose
+    triple product (N - CA) . ((C - CA) x (CB - CA)) is positive, per population and centre: float64 numpy
+    ``[P, n_centres]`` (``dihedral_angles`` and ``weighted_mean`` of the indicator; NaN where a population's weight sum is
+    0).  Which sign is the L form is not decided here: compare with a structure of known handedness.  A reflection of
+    the coordinates turns f into 1 - f."""
+    import numpy as np
+
+    theta = dihedral_angles(samples, quads)
+    positive = torch.where(torch.isnan(theta), theta, (theta > 0).float())  # a NaN angle leaves the walker out (n_bad)
+    return np.stack([weighted_mean(positive[:, k].contiguous(), logweights, populations)["mean"]
+                     for k in range(theta.shape[1])], axis=1)
+
+
+class DihedralHistogram(WeightedHistogram):
+    """Result of ``ramachandran_histogram`` for P populations and n_pair angle pairs: ``raw``, ``counts`` (int64) and
+    ``weights`` (float64) of shape ``[P, n_pair, nb_a, nb_b]`` on the device, ``log_scale``, ``n_bad``, ``n_neg_inf`` and
+    ``shift`` as in ``WeightedHistogram``, and the float32 numpy bin edges ``edges_a`` / ``edges_b`` of the two axes."""
+
+    def __init__(self, raw, counts, info, edges_a, edges_b):
+        super().__init__(raw, counts, info)
+        self.edges_a, self.edges_b = edges_a, edges_b
+
+    def density(self):
+        """Self-normalised 2-D density per population and pair, numpy float64 ``[P, n_pair, nb_a, nb_b]``: weights over
+        (cell area * the pair's weight sum), so that it integrates to 1 over the edges; NaN where that sum is 0."""
+        import numpy as np
+
+        w = self.weights.cpu().numpy()
+        area = np.outer(np.array(np.diff(self.edges_a), float), np.array(np.diff(self.edges_b), float))
+        tot = w.sum(axis=(2, 3), keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tot > 0, w / area / tot, np.nan)
+
+    def marginal(self, axis: int):
+        """Exact integer marginals ``(raw, counts)``, int64 ``[P, n_pair, nb]`` on the device: axis 0 keeps the a-axis
+        (sums over b), axis 1 the b-axis."""
+        if axis not in (0, 1):
+            raise ValueError(f"marginal: axis must be 0 (a) or 1 (b), got {axis}")
+        return self.raw.sum(dim=3 - axis), self.counts.sum(dim=3 - axis)
+
+
+def ramachandran_histogram(samples: torch.Tensor, pair_quads, bins: int = 64, logweights: torch.Tensor = None,
+                           populations: int = 1, energy_function=None, edges=None) -> DihedralHistogram:
+    """Importance-weighted 2-D histograms of dihedral pairs per population, from the coordinates in one call
+    (pita_dihedral_histogram2d; the angles are never written).  ``pair_quads``: ``[n_pair, 2, 4]`` as ``phi_psi_quads``
+    returns them (or one pair ``[2, 4]``, e.g. ``ALDP_PHI_PSI``), first axis a, second axis b.  ``edges``: None = ``bins``
+    equal bins over [-pi, pi] on both axes (``numpy.linspace(-pi, pi, bins + 1).astype(float32)``), one ascending array
+    for both axes, or a pair ``(edges_a, edges_b)``; bins as ``histogram`` counts them, so +pi falls into the last bin
+    (no wrap-around).  ``samples``, ``energy_function`` as in ``dihedral_angles``; ``logweights``, ``populations`` and the
+    order-independent fixed-point sums as in ``weighted_histogram``.  At most 4096 cells (64 x 64) per pair."""
+    import numpy as np
+    from . import _lib
+
+    # host-side checks first: the split into populations, the edges, then (in _dihedral_args) the shapes and the indices
+    _population_args(samples.shape[0], None, populations, None)
+    if edges is None:
+        ea = eb = np.linspace(-np.pi, np.pi, int(bins) + 1).astype(np.float32)
+    elif isinstance(edges, (tuple, list)) and len(edges) == 2 and np.ndim(edges[0]) == 1:
+        ea, eb = (np.asarray(e, dtype=np.float32) for e in edges)
+    else:
+        ea = eb = np.asarray(edges, dtype=np.float32)
+    for e in (ea, eb):
+        if e.ndim != 1 or e.size < 2 or not (np.diff(e) > 0).all():
+            raise ValueError("edges: expected ascending 1-D arrays of at least two entries")
+    x, n, q = _dihedral_args(samples, pair_quads, (2, 4), energy_function)
+    P, S, lw = _population_args(x.shape[0], logweights, populations, x.device)
+    ta, tb = (torch.from_numpy(np.ascontiguousarray(e)).to(x.device) for e in (ea, eb))
+    shape = (P, q.shape[0], ea.size - 1, eb.size - 1)
+    raw, counts = (torch.empty(shape, dtype=torch.int64, device=x.device) for _ in range(2))
+    info = torch.empty(P, 4, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().pita_dihedral_histogram2d(x.data_ptr(), _lib.ptr(lw), P, S, n, q.data_ptr(), q.shape[0], ta.data_ptr(),
+                                                    shape[2], tb.data_ptr(), shape[3], raw.data_ptr(), counts.data_ptr(),
+                                                    info.data_ptr(), _lib.stream_ptr(x.device)), "pita_dihedral_histogram2d")
+    return DihedralHistogram(raw, counts, info, ea, eb)
