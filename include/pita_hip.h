@@ -121,6 +121,33 @@ int pita_dw_mala(float* x, float* logp, const float* noise /*nullable*/, const f
                  const int64_t* walker_ids /*nullable*/, int64_t step0, int remove_mean, float* rates_out /*nullable*/,
                  void* workspace, void* stream);
 
+/* The same chains with one step size, one acceptance count and one adaptation PER POPULATION, for batches that are n_pop
+ * independent populations of pop_size consecutive Philox walker keys (WeightedSDEIntegrator(populations=P,
+ * mcmc_per_population=True)).  Population of row w: (key - pop_base) / pop_size with key = walker_ids[w] or
+ * walker_offset + w and pop_base the key of the first row of the call's first population; the caller guarantees
+ * 0 <= population < n_pop (device ids cannot be checked without a host read).  In place of `total`: totals (device
+ * int64 [n_pop]: the walkers each population's rates are taken over, i.e. its rows in this call).  dt_dev is fp64 [n_pop]
+ * (in: step sizes, out: final step sizes), rates_out fp32 [nsteps, n_pop], workspace 8-byte aligned device scratch of
+ * pita_mala_pop_workspace_bytes(nsteps, n_pop) bytes (one size function for the pair targets and the force field).
+ * A population's walkers, rates and final step size are bit-identical to pita_*_mala on that population's rows alone
+ * (total = its row count); a population with totals[p] == 0 keeps dt_dev[p] and gets NaN rates.  Launches as above: one
+ * for a non-adaptive chain, one per step for an adaptive one, no grid-wide barrier, no wait; every walker replays the
+ * adaptation of its own population, and a block's count is split by population before it reaches memory (integer adds).
+ * dt_dev, totals, workspace non-null, B >= 0, nsteps >= 0, n_pop >= 1, pop_size >= 1 and the workspace alignment are
+ * checked before any device call (PITA_EINVAL); geometries without a fused chain answer PITA_EUNSUPPORTED as above. */
+size_t pita_mala_pop_workspace_bytes(int nsteps, int n_pop);
+int pita_lj_mala_pop(float* x, float* logp, const float* noise /*nullable*/, const float* uniforms /*nullable*/, int64_t B,
+                     int n_particles, int n_dim, float temperature, float energy_factor, float dist_eps, float eps,
+                     float rm, float osc_scale, int nsteps, double* dt_dev, int adaptive, const int64_t* totals, int n_pop,
+                     int64_t pop_size, uint64_t pop_base, uint64_t seed, uint64_t walker_offset,
+                     const int64_t* walker_ids /*nullable*/, int64_t step0, int remove_mean,
+                     float* rates_out /*nullable*/, void* workspace, void* stream);
+int pita_dw_mala_pop(float* x, float* logp, const float* noise /*nullable*/, const float* uniforms /*nullable*/, int64_t B,
+                     int n_particles, int n_dim, float temperature, float a, float b, float c, float d0, int nsteps,
+                     double* dt_dev, int adaptive, const int64_t* totals, int n_pop, int64_t pop_size, uint64_t pop_base,
+                     uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids /*nullable*/, int64_t step0,
+                     int remove_mean, float* rates_out /*nullable*/, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- wide EGNN backbone (hidden_nf <= 64, static node features)
  * replaces EGNN_dynamics_AD2_cat.forward (pita/src/models/components/egnn_dynamics_ad2_cat.py:157-203; the
  * alanine-dipeptide backbone of configs/model/net/egnn_dynamics_ad2_cat.yaml: hidden 64 x 5 layers, one-hot atom-type
@@ -331,6 +358,17 @@ int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* noise /*null
                  const float* uniforms /*nullable [n_steps,B]*/, int64_t B, int n_steps, double* dt_dev, int adaptive,
                  int64_t total, uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids /*nullable*/,
                  int64_t step0, int remove_mean, float* rates_out /*nullable*/, void* workspace, void* stream);
+
+/* pita_ff_mala with one step size, count and adaptation per population: contract and arguments of pita_lj_mala_pop
+ * (totals / n_pop / pop_size / pop_base in place of total, dt_dev [n_pop], rates_out [n_steps, n_pop], workspace of
+ * pita_mala_pop_workspace_bytes(n_steps, n_pop) bytes), bit-identical per population to pita_ff_mala on its rows alone.
+ * ff, dt_dev, totals, workspace non-null, B >= 0, n_steps >= 0, n_pop >= 1, pop_size >= 1 and the workspace alignment are
+ * checked before any device call (PITA_EINVAL); B == 0 or n_steps == 0 is PITA_OK and leaves dt_dev as it is. */
+int pita_ff_mala_pop(pita_ff_t* ff, float* x, float* logp, const float* noise /*nullable [n_steps,B,3n]*/,
+                     const float* uniforms /*nullable [n_steps,B]*/, int64_t B, int n_steps, double* dt_dev, int adaptive,
+                     const int64_t* totals, int n_pop, int64_t pop_size, uint64_t pop_base, uint64_t seed,
+                     uint64_t walker_offset, const int64_t* walker_ids /*nullable*/, int64_t step0, int remove_mean,
+                     float* rates_out /*nullable*/, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------- EGNN backbone (K5, K7)
  * replaces EGNN_dynamics.forward (pita/src/models/components/egnn_temp_conditioned.py:56-93,
@@ -643,6 +681,22 @@ int pita_mala_accept(float* x, float* logp, const float* force, const float* x_p
                      const double* dt_dev, uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids /*nullable*/,
                      int64_t step, int remove_mean, int* acc_count, void* stream);
 int pita_mala_adapt(double* dt_dev, int* acc_count, int64_t total, int adaptive, float* rate_out, void* stream);
+/* The three steps per population (see pita_lj_mala_pop for the population of a row): dt_dev fp64 [n_pop] and acc_count
+ * int [n_pop]; propose and accept read dt_dev[population of the row], accept adds into acc_count[population]; adapt runs
+ * the rule above, in the same arithmetic, for every population against totals (device int64 [n_pop]) -> rate_out [n_pop]
+ * (nullable) and zeroes acc_count.  A population with totals[p] == 0 keeps its dt and gets a NaN rate.  Null dt_dev /
+ * acc_count / totals, n_pop < 1, pop_size < 1 and B < 0 are PITA_EINVAL before any device call. */
+int pita_mala_propose_pop(const float* x, const float* force, float* x_prop, const float* noise, int64_t B,
+                          int n_particles, int n_dim, const double* dt_dev, int n_pop, int64_t pop_size, uint64_t pop_base,
+                          uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids /*nullable*/, int64_t step,
+                          void* stream);
+int pita_mala_accept_pop(float* x, float* logp, const float* force, const float* x_prop, const float* logp_prop,
+                         const float* force_prop, const float* uniforms, int64_t B, int n_particles, int n_dim,
+                         const double* dt_dev, int n_pop, int64_t pop_size, uint64_t pop_base, uint64_t seed,
+                         uint64_t walker_offset, const int64_t* walker_ids /*nullable*/, int64_t step, int remove_mean,
+                         int* acc_count, void* stream);
+int pita_mala_adapt_pop(double* dt_dev, int* acc_count, const int64_t* totals, int n_pop, int adaptive, float* rate_out,
+                        void* stream);
 
 /* ---------------------------------------------------------------- resampling (K10, K11)
  * K10 systematic resampling, replaces sample_cat_sys (utils.py:111-120): weights =

@@ -73,6 +73,13 @@ _PROTOS = {
     "pita_dw_mala": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int] + [c_float] * 5 +
                      [c_int, c_void_p, c_int, c_int64, c_uint64, c_uint64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                       c_void_p]),
+    "pita_mala_pop_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "pita_lj_mala_pop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int] + [c_float] * 6 +
+                         [c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_int64,
+                          c_int, c_void_p, c_void_p, c_void_p]),
+    "pita_dw_mala_pop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int] + [c_float] * 5 +
+                         [c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_int64,
+                          c_int, c_void_p, c_void_p, c_void_p]),
     "pita_gmm_logp_force": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_float,
                                     c_void_p]),
     "pita_ff_create": (c_int, [POINTER(c_void_p), POINTER(FfConfig)]),
@@ -83,6 +90,9 @@ _PROTOS = {
     "pita_ff_mala_workspace_bytes": (c_size_t, [c_int]),
     "pita_ff_mala": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_int64,
                              c_uint64, c_uint64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "pita_ff_mala_pop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                 c_void_p, c_int, c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_int64, c_int, c_void_p,
+                                 c_void_p, c_void_p]),
     "pita_egnn_create": (c_int, [POINTER(c_void_p), POINTER(EgnnConfig), c_void_p, c_int64]),
     "pita_egnn_destroy": (c_int, [c_void_p]),
     "pita_egnn_num_weights": (c_int64, [POINTER(EgnnConfig)]),
@@ -149,6 +159,11 @@ _PROTOS = {
     "pita_mala_accept": (c_int, [c_void_p] * 7 + [c_int64, c_int, c_int, c_void_p, c_uint64, c_uint64, c_void_p, c_int64,
                                                   c_int, c_void_p, c_void_p]),
     "pita_mala_adapt": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "pita_mala_propose_pop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int,
+                                      c_int64, c_uint64, c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
+    "pita_mala_accept_pop": (c_int, [c_void_p] * 7 + [c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_uint64, c_uint64,
+                                                      c_uint64, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "pita_mala_adapt_pop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "pita_resample_workspace_bytes": (c_size_t, [c_int64]),
     "pita_systematic_resample": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
     "pita_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),

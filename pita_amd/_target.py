@@ -33,9 +33,13 @@ walker_ids=None, step0=0,   the rates are taken over; ``walker_ids`` (int64 [B] 
 remove_mean=True,           keys of compacted batches.  Returns ``x`` when it ran; None means "not
 rates_out=None)``           mine" (no fused chain for this geometry or plan, PITA_EUNSUPPORTED from the
                             library included): nothing was changed and the integrator runs the
-                            launch-per-kernel chain, which gives the same bits.  Absent: that chain
+                            launch-per-kernel chain, which gives the same bits.  Absent: that chain.
+                            ``total`` may instead be a ``MalaPopulations`` record: the chain then keeps
+                            one step size, count and adaptation per population (the ``_pop`` entry
+                            points), ``dt_dev`` is fp64 [P] and ``rates_out`` fp32 [>= num_steps, P]
 ==========================  ==========================================================================  ============
 """
+import collections
 import contextlib
 
 import torch
@@ -46,7 +50,14 @@ _U64 = 0xFFFFFFFFFFFFFFFF
 # The workspace of every fused chain is sized by one native function (pair_common.h: mala_workspace_bytes) behind two
 # exports; the pair targets (lj, dw) take this one, the force field its own pita_ff_mala_workspace_bytes.
 PAIR_MALA_WORKSPACE = "pita_lj_mala_workspace_bytes"
+# ... and the per-population chains of every target this one, of (steps, populations)
+POP_MALA_WORKSPACE = "pita_mala_pop_workspace_bytes"
 _SAME_DEVICE = contextlib.nullcontext()
+
+# ``total`` of a per-population chain: populations of ``size`` consecutive Philox walker keys from key ``base`` on (the
+# key of the first row of the call's first population); ``totals``: int64 [P] on the device, the rows of each population
+# in the call.  Row w belongs to population (key(w) - base) // size, which the caller keeps in [0, P).
+MalaPopulations = collections.namedtuple("MalaPopulations", "size base totals")
 
 
 def _device_guard(device):
@@ -54,6 +65,23 @@ def _device_guard(device):
     tensor's): torch's context manager when another device is current, nothing to enter when it already is -- these
     bodies run once per launch, and the target kernels are launches of a few microseconds."""
     return _SAME_DEVICE if device.index == torch.cuda.current_device() else torch.cuda.device(device)
+
+
+def _check_populations(pops, steps, dt_dev, rates_out):
+    """The shapes a per-population chain writes through: P, or ValueError before anything reaches the library."""
+    t = pops.totals
+    if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1 or not t.is_contiguous():
+        raise ValueError("MalaPopulations.totals must be a contiguous int64 [P] tensor, P >= 1")
+    P = t.numel()
+    if int(pops.size) < 1 or int(pops.base) < 0:
+        raise ValueError(f"MalaPopulations: size >= 1 and base >= 0, got size {pops.size}, base {pops.base}")
+    if dt_dev.dtype != torch.float64 or dt_dev.numel() != P or not dt_dev.is_contiguous():
+        raise ValueError(f"per-population chain: dt_dev must be fp64 [{P}], got {dt_dev.dtype} {tuple(dt_dev.shape)}")
+    if rates_out is not None and (rates_out.dtype != torch.float32 or rates_out.dim() != 2 or rates_out.shape[1] != P or
+                                  rates_out.shape[0] < steps or not rates_out.is_contiguous()):
+        raise ValueError(f"per-population chain: rates_out must be fp32 [>= {steps}, {P}], got {rates_out.dtype} "
+                         f"{tuple(rates_out.shape)}")
+    return P
 
 
 class HipTarget:
@@ -98,13 +126,21 @@ class HipTarget:
     def _mala_call(self, symbol, workspace_symbol, x, logp, head_args, num_steps, dt_dev, adaptive, total, noise, uniforms,
                    seed, walker_offset, walker_ids, step0, remove_mean, rates_out):
         """pita_{lj,dw,ff}_mala([handle,] x, logp, noise, uniforms, B, *head_args, steps, dt_dev, ..., workspace, stream)
-        -> x, or None when the library answers PITA_EUNSUPPORTED."""
+        -> x, or None when the library answers PITA_EUNSUPPORTED.  ``total``: the walker count, or a ``MalaPopulations``
+        record -- then the call goes to ``symbol + "_pop"`` with (totals, P, size, base) in the place of the count."""
         L = lib()
-        ws = torch.empty((int(getattr(L, workspace_symbol)(int(num_steps))) + 7) // 8, device=x.device, dtype=torch.int64)
+        steps = int(num_steps)
+        if isinstance(total, MalaPopulations):
+            P = _check_populations(total, steps, dt_dev, rates_out)
+            symbol, ws_bytes = symbol + "_pop", getattr(L, POP_MALA_WORKSPACE)(steps, P)
+            over = (total.totals.data_ptr(), P, int(total.size), int(total.base))
+        else:
+            ws_bytes, over = getattr(L, workspace_symbol)(steps), (int(total),)
+        ws = torch.empty((int(ws_bytes) + 7) // 8, device=x.device, dtype=torch.int64)
         with _device_guard(x.device):
             rc = getattr(L, symbol)(*self._handle_args(), x.data_ptr(), logp.data_ptr(), ptr(noise), ptr(uniforms),
-                                    x.shape[0], *head_args, int(num_steps), dt_dev.data_ptr(), int(bool(adaptive)),
-                                    int(total), int(seed) & _U64, int(walker_offset), ptr(walker_ids), int(step0),
+                                    x.shape[0], *head_args, steps, dt_dev.data_ptr(), int(bool(adaptive)),
+                                    *over, int(seed) & _U64, int(walker_offset), ptr(walker_ids), int(step0),
                                     int(bool(remove_mean)), ptr(rates_out), ws.data_ptr(), stream_ptr(x.device))
         if rc == PITA_EUNSUPPORTED:
             return None

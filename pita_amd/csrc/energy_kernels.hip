@@ -713,9 +713,12 @@ __global__ void __launch_bounds__(256, 2) lj13_descent_kernel(float* __restrict_
 // before, is one launch per step (stream order is the barrier), each deriving its step size from dt_dev[0] and the
 // counts so far (mala_replay_dt).
 
-template <bool UNIT_RM>
+// POP (pita_lj_mala_pop): every walker takes its step size from its own population (MalaPopParams, pair_common.h) and a
+// tile's count is split by population, wave by wave, before it reaches memory: a tile of 128 consecutive rows can
+// straddle populations.
+template <bool UNIT_RM, bool POP = false>
 __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x, float* __restrict__ logp, long long B,
-                                                           PairParams p, MalaParams q) {
+                                                           PairParams p, MalaQ<POP> q) {
   constexpr int D = 39, WPB = 128, N = 13;
   __shared__ __attribute__((aligned(16))) float xs[WPB * D];   // current walkers
   __shared__ __attribute__((aligned(16))) float xps[WPB * D];  // proposals
@@ -725,9 +728,10 @@ __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x
   const int tid = threadIdx.x;
   const int half = tid / WPB, wl = tid - half * WPB;
   const long long nblk = (B + WPB - 1) / WPB;  // tiles of 128 walkers; a tile stays in LDS for all steps of the launch
-  const double dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
+  double dt = 0.0;
+  if constexpr (!POP) dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
   long long w0 = 0, wg = 0;
-  int nw = 0, nfl = 0, row = 0;
+  int nw = 0, nfl = 0, row = 0, pop = 0;
   bool act = false;
   unsigned long long key = 0;
   float lp = 0.f;
@@ -747,6 +751,10 @@ __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x
     wg = w0 + (act ? wl : 0);
     key = q.walker_ids ? (unsigned long long)q.walker_ids[wg] : q.walker_offset + (unsigned long long)wg;
     lp = (half == 0 && act) ? logp[wg] : 0.f;
+    if constexpr (POP) {
+      pop = mala_pop_of(q, key);
+      dt = mala_replay_dt(q, pop);
+    }
   };
   auto store = [&]() {
     {
@@ -854,6 +862,14 @@ __global__ void __launch_bounds__(256, 2) lj13_mala_kernel(float* __restrict__ x
 #pragma unroll
         for (int k = 0; k < 39; ++k) xs[row + k] = fr[k];
       }
+      if constexpr (POP) {
+        mala_count_by_pop(half == 0 && act, acc, pop, [&](int pl, int c) {
+          __hip_atomic_fetch_add(&q.sync[(long long)s * q.n_pop + pl], (unsigned long long)c, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+        });
+        __syncthreads();
+        return 0;
+      }
       const unsigned long long bal = __ballot(acc);
       if ((tid & 63) == 0) cnt[tid >> 6] = __popcll(bal);
       __syncthreads();
@@ -879,6 +895,30 @@ int launch_mala_finish(double* dt_dev, const unsigned long long* sync, int nstep
                        float* rates_out, void* stream) {
   hipLaunchKernelGGL(mala_finish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dt_dev, sync, nsteps, total, adaptive,
                      rates_out);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// the same per population, one thread each: column p of the counts, mala_adapt_pop_kernel's rule (sampler_kernels.hip)
+__global__ void __launch_bounds__(64) mala_finish_pop_kernel(double* dt_dev, const unsigned long long* sync, int nsteps,
+                                                             const long long* totals, int n_pop, int adaptive,
+                                                             float* rates_out) {
+  const int pop = blockIdx.x * 64 + threadIdx.x;
+  if (pop >= n_pop) return;
+  const long long total = totals[pop];
+  double dt = dt_dev[pop];
+  for (int s = 0; s < nsteps; ++s) {
+    const float rate = total > 0 ? (float)(int)sync[(long long)s * n_pop + pop] / (float)total : NAN;
+    if (rates_out) rates_out[(long long)s * n_pop + pop] = rate;
+    if (adaptive && total > 0) dt = ((double)rate > 0.55) ? dt * 1.1 : dt / 1.1;
+  }
+  dt_dev[pop] = dt;
+}
+
+int launch_mala_finish(double* dt_dev, const unsigned long long* sync, int nsteps, const long long* totals, int n_pop,
+                       int adaptive, float* rates_out, void* stream) {
+  hipLaunchKernelGGL(mala_finish_pop_kernel, dim3((unsigned)((n_pop + 63) / 64)), dim3(64), 0, (hipStream_t)stream, dt_dev,
+                     sync, nsteps, totals, n_pop, adaptive, rates_out);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }
@@ -1094,6 +1134,37 @@ extern "C" int pita_dw_descent(float* x, const float* noise, int64_t B, int n, i
 
 extern "C" size_t pita_lj_mala_workspace_bytes(int nsteps) { return mala_workspace_bytes(nsteps); }
 
+extern "C" size_t pita_mala_pop_workspace_bytes(int nsteps, int n_pop) { return mala_pop_workspace_bytes(nsteps, n_pop); }
+
+// The launches of a chain on the LJ targets, for one step size (Q = MalaParams) or one per population (MalaPopParams).
+template <class Q>
+static int lj_mala_chain(const char* who, float* x, float* logp, int64_t B, int n, int d, const PairParams& p, Q& q,
+                         int nsteps, double* dt_dev, float* rates_out, void* stream) {
+  constexpr bool POP = std::is_same<Q, MalaPopParams>::value;
+  if (n == 55) {
+    return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
+      if (B == 0) return (int)PITA_OK;
+      const int rc = ring_launch_mala(E_LJ, x, logp, B, n, d, p, q, stream);
+      return rc == 1 ? fail(PITA_EUNSUPPORTED, "%s: no ring kernel for n = %d", who, n) : rc;
+    });
+  }
+  // one residency of the chain kernel: a performance choice (no tail wave), nothing depends on co-residency
+  int per_cu = 0, cus = 0;
+  if (int rc = resident_blocks(lj13_mala_kernel<true, POP>, 256, 0, per_cu)) return rc;
+  if (int rc = device_cus(cus)) return rc;
+  const long long nblk = (B + 127) / 128;
+  const unsigned grid = capped_grid(nblk, (long long)per_cu * cus);
+  return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
+    if (nblk == 0) return (int)PITA_OK;
+    dispatch_bool(p.rm2 == 1.0f, [&](auto unit) {
+      hipLaunchKernelGGL((lj13_mala_kernel<decltype(unit)::value, POP>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
+                         logp, (long long)B, p, q);
+    });
+    PITA_LAUNCH_CHECK();
+    return (int)PITA_OK;
+  });
+}
+
 // The pair-target chains (frame: run_mala_chain, pair_common.h).  With B == 0 the chain launches nothing but the finish
 // kernel still runs (rates 0, dt adapted on them): kept as it was.
 extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const float* uniforms, int64_t B, int n, int d,
@@ -1110,28 +1181,25 @@ extern "C" int pita_lj_mala(float* x, float* logp, const float* noise, const flo
   const PairParams p = lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale);
   MalaParams q = mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, total, dt_dev, adaptive, remove_mean,
                              workspace);
-  if (n == 55) {
-    return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
-      if (B == 0) return (int)PITA_OK;
-      const int rc = ring_launch_mala(E_LJ, x, logp, B, n, d, p, q, stream);
-      return rc == 1 ? fail(PITA_EUNSUPPORTED, "pita_lj_mala: no ring kernel for n = %d", n) : rc;
-    });
-  }
-  // one residency of the chain kernel: a performance choice (no tail wave), nothing depends on co-residency
-  int per_cu = 0, cus = 0;
-  if (int rc = resident_blocks(lj13_mala_kernel<true>, 256, 0, per_cu)) return rc;
-  if (int rc = device_cus(cus)) return rc;
-  const long long nblk = (B + 127) / 128;
-  const unsigned grid = capped_grid(nblk, (long long)per_cu * cus);
-  return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
-    if (nblk == 0) return (int)PITA_OK;
-    dispatch_bool(p.rm2 == 1.0f, [&](auto unit) {
-      hipLaunchKernelGGL(lj13_mala_kernel<decltype(unit)::value>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, logp,
-                         (long long)B, p, q);
-    });
-    PITA_LAUNCH_CHECK();
-    return (int)PITA_OK;
-  });
+  return lj_mala_chain("pita_lj_mala", x, logp, B, n, d, p, q, nsteps, dt_dev, rates_out, stream);
+}
+
+extern "C" int pita_lj_mala_pop(float* x, float* logp, const float* noise, const float* uniforms, int64_t B, int n, int d,
+                                float temperature, float energy_factor, float dist_eps, float eps, float rm,
+                                float osc_scale, int nsteps, double* dt_dev, int adaptive, const int64_t* totals, int n_pop,
+                                int64_t pop_size, uint64_t pop_base, uint64_t seed, uint64_t walker_offset,
+                                const int64_t* walker_ids, int64_t step0, int remove_mean, float* rates_out,
+                                void* workspace, void* stream) {
+  PITA_REQUIRE(temperature > 0.f, "pita_lj_mala_pop: temperature must be > 0");
+  if (int rc = check_mala_pop_args("pita_lj_mala_pop", B, nsteps, dt_dev, totals, n_pop, pop_size, workspace)) return rc;
+  if (!((n == 13 || n == 55) && d == 3))
+    return fail(PITA_EUNSUPPORTED, "pita_lj_mala_pop: fused chains exist for LJ13 and LJ55 (n = %d, d = %d)", n, d);
+  if (nsteps == 0) return PITA_OK;
+  PITA_REQUIRE(B == 0 || (x && logp), "pita_lj_mala_pop: null argument (x, logp)");
+  const PairParams p = lj_params(temperature, energy_factor, dist_eps, eps, rm, osc_scale);
+  MalaPopParams q = mala_pop_params(mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, 0, dt_dev, adaptive,
+                                                remove_mean, workspace), nsteps, totals, n_pop, pop_size, pop_base);
+  return lj_mala_chain("pita_lj_mala_pop", x, logp, B, n, d, p, q, nsteps, dt_dev, rates_out, stream);
 }
 
 extern "C" int pita_dw_mala(float* x, float* logp, const float* noise, const float* uniforms, int64_t B, int n, int d,
@@ -1152,5 +1220,26 @@ extern "C" int pita_dw_mala(float* x, float* logp, const float* noise, const flo
     if (B == 0) return (int)PITA_OK;
     const int rc = ring_launch_mala(E_DW, x, logp, B, n, d, p, q, stream);
     return rc == 1 ? fail(PITA_EUNSUPPORTED, "pita_dw_mala: no ring kernel for n = %d", n) : rc;
+  });
+}
+
+extern "C" int pita_dw_mala_pop(float* x, float* logp, const float* noise, const float* uniforms, int64_t B, int n, int d,
+                                float temperature, float a, float b, float c, float d0, int nsteps, double* dt_dev,
+                                int adaptive, const int64_t* totals, int n_pop, int64_t pop_size, uint64_t pop_base,
+                                uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids, int64_t step0,
+                                int remove_mean, float* rates_out, void* workspace, void* stream) {
+  PITA_REQUIRE(temperature > 0.f, "pita_dw_mala_pop: temperature must be > 0");
+  if (int rc = check_mala_pop_args("pita_dw_mala_pop", B, nsteps, dt_dev, totals, n_pop, pop_size, workspace)) return rc;
+  if (!(n == 4 && d == 2))
+    return fail(PITA_EUNSUPPORTED, "pita_dw_mala_pop: the fused chain exists for DW4 (n = %d, d = %d)", n, d);
+  if (nsteps == 0) return PITA_OK;
+  PITA_REQUIRE(B == 0 || (x && logp), "pita_dw_mala_pop: null argument (x, logp)");
+  const PairParams p = dw_params(temperature, a, b, c, d0);
+  MalaPopParams q = mala_pop_params(mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, 0, dt_dev, adaptive,
+                                                remove_mean, workspace), nsteps, totals, n_pop, pop_size, pop_base);
+  return run_mala_chain(nsteps, dt_dev, rates_out, q, stream, [&]() {
+    if (B == 0) return (int)PITA_OK;
+    const int rc = ring_launch_mala(E_DW, x, logp, B, n, d, p, q, stream);
+    return rc == 1 ? fail(PITA_EUNSUPPORTED, "pita_dw_mala_pop: no ring kernel for n = %d", n) : rc;
   });
 }

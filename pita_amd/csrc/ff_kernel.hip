@@ -400,7 +400,10 @@ __global__ void __launch_bounds__(FF_THREADS) ff_kernel(FfParams p) {
 // steps before it (mala_replay_dt); the frame around the launches is run_mala_chain (pair_common.h), shared with the
 // pair-target chains: mala_finish_kernel runs last and leaves the rates and the final step size.
 // x [B][3 n] walkers and logp [B] their log-densities, both updated in place; q as for the pair-target chains (pair_common.h).
-__global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* x, float* logp, long long B, MalaParams q) {
+// POP (pita_ff_mala_pop): a walker's step size is its population's (MalaPopParams), the walkers' populations sit behind
+// the accept flags in gs (n >= 2 leaves the room), and thread 0 adds a tile's count run by run of equal populations.
+template <bool POP = false>
+__global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* x, float* logp, long long B, MalaQ<POP> q) {
   extern __shared__ float sm[];
   const int n = p.n, D = 3 * n, WPB = p.wpb;
   const FfLds L = ff_stage(p, sm);
@@ -408,9 +411,13 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* 
   float *qf = L.gs, *qb = qf + WPB * n, *flag = qb + WPB * n;  // [WPB][n] partial |x' - fwd mean|^2, |x - bwd mean|^2; [WPB] 1.0 = accepted
   const int tid = threadIdx.x, wl = tid / n, a = tid - wl * n;
   const bool lane_on = wl < WPB;
+  int* popl = reinterpret_cast<int*>(flag + WPB);  // POP: [WPB] population of the tile's walkers
   // step size of step `step_base`: constant, or adapted on the acceptance rates of the steps before
-  const double dtd = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
-  const float hdt = (float)(0.5 * dtd), sdt = (float)sqrt(dtd), tdt = (float)(2.0 * dtd);
+  float hdt = 0.f, sdt = 0.f, tdt = 0.f;
+  if constexpr (!POP) {
+    const double dtd = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
+    hdt = (float)(0.5 * dtd); sdt = (float)sqrt(dtd); tdt = (float)(2.0 * dtd);
+  }
   const float sc = -p.inv_kT * p.length_scale;  // d logp / d x_model
   const long long nblk = (B + WPB - 1) / WPB;
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -422,6 +429,12 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* 
     const long long wg = w0 + (act ? wl : 0);
     const unsigned long long key = q.walker_ids ? (unsigned long long)q.walker_ids[wg] : q.walker_offset + (unsigned long long)wg;
     float lp = (act && a == 0) ? logp[wg] : 0.f;
+    if constexpr (POP) {
+      const int pop = mala_pop_of(q, key);
+      const double dtd = mala_replay_dt(q, pop);
+      hdt = (float)(0.5 * dtd); sdt = (float)sqrt(dtd); tdt = (float)(2.0 * dtd);
+      if (act && a == 0) popl[wl] = pop;  // read by thread 0 behind the barriers of the step
+    }
     for (int st = 0; st < q.steps; ++st) {
       const int s = q.step_base + st;
       // ---- F at x
@@ -494,8 +507,19 @@ __global__ void __launch_bounds__(FF_THREADS) ff_mala_kernel(FfParams p, float* 
       }
       if (tid == 0) {  // integer add: the step's count does not depend on the order of the blocks
         int c = 0;
-        for (int j = 0; j < nw; ++j) c += flag[j] != 0.f;
-        if (c) atomicAdd(&q.sync[s], (unsigned long long)c);
+        if constexpr (POP) {
+          unsigned long long* row = q.sync + (long long)s * q.n_pop;
+          for (int j = 0; j < nw; ++j) {
+            c += flag[j] != 0.f;
+            if (c && (j + 1 == nw || popl[j + 1] != popl[j])) {
+              atomicAdd(&row[popl[j]], (unsigned long long)c);
+              c = 0;
+            }
+          }
+        } else {
+          for (int j = 0; j < nw; ++j) c += flag[j] != 0.f;
+          if (c) atomicAdd(&q.sync[s], (unsigned long long)c);
+        }
       }
       __syncthreads();
       if (act) {
@@ -727,6 +751,21 @@ extern "C" int pita_ff_descent(pita_ff_t* ff, float* x, const float* noise, int6
 
 extern "C" size_t pita_ff_mala_workspace_bytes(int n_steps) { return mala_workspace_bytes(n_steps); }
 
+// the launches of a chain on the handle's plan (the plan of pita_ff_descent: the chain lives in the descent's LDS footprint)
+template <class Q>
+static int ff_mala_chain(pita_ff_t* ff, float* x, float* logp, int64_t B, int n_steps, double* dt_dev, float* rates_out, Q& q,
+                         void* stream) {
+  constexpr bool POP = std::is_same<Q, MalaPopParams>::value;
+  const FfParams p = ff->p;
+  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_mala_kernel<POP>), ff->lds_descent));
+  return run_mala_chain(n_steps, dt_dev, rates_out, q, stream, [&]() {
+    hipLaunchKernelGGL(ff_mala_kernel<POP>, dim3(ff_grid(p, B)), dim3(FF_THREADS), ff->lds_descent, (hipStream_t)stream, p, x,
+                       logp, (long long)B, q);
+    PITA_LAUNCH_CHECK();
+    return (int)PITA_OK;
+  });
+}
+
 extern "C" int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* noise, const float* uniforms, int64_t B,
                             int n_steps, double* dt_dev, int adaptive, int64_t total, uint64_t seed, uint64_t walker_offset,
                             const int64_t* walker_ids, int64_t step0, int remove_mean, float* rates_out, void* workspace,
@@ -736,14 +775,22 @@ extern "C" int pita_ff_mala(pita_ff_t* ff, float* x, float* logp, const float* n
   PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_ff_mala: workspace must be 8-byte aligned");
   if (B == 0 || n_steps == 0) return PITA_OK;  // unlike the pair chains, an empty batch leaves dt_dev and rates_out untouched
   PITA_REQUIRE(x && logp, "pita_ff_mala: null argument (x, logp)");
-  const FfParams p = ff->p;  // the plan of pita_ff_descent: the chain lives in the descent's LDS footprint
   MalaParams q = mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, total, dt_dev, adaptive, remove_mean,
                              workspace);
-  PITA_HIP_CHECK(ensure_dynamic_lds(reinterpret_cast<const void*>(ff_mala_kernel), ff->lds_descent));
-  return run_mala_chain(n_steps, dt_dev, rates_out, q, stream, [&]() {
-    hipLaunchKernelGGL(ff_mala_kernel, dim3(ff_grid(p, B)), dim3(FF_THREADS), ff->lds_descent, (hipStream_t)stream, p, x, logp,
-                       (long long)B, q);
-    PITA_LAUNCH_CHECK();
-    return (int)PITA_OK;
-  });
+  return ff_mala_chain(ff, x, logp, B, n_steps, dt_dev, rates_out, q, stream);
+}
+
+extern "C" int pita_ff_mala_pop(pita_ff_t* ff, float* x, float* logp, const float* noise, const float* uniforms, int64_t B,
+                                int n_steps, double* dt_dev, int adaptive, const int64_t* totals, int n_pop,
+                                int64_t pop_size, uint64_t pop_base, uint64_t seed, uint64_t walker_offset,
+                                const int64_t* walker_ids, int64_t step0, int remove_mean, float* rates_out,
+                                void* workspace, void* stream) {
+  PITA_REQUIRE(ff, "pita_ff_mala_pop: null argument (handle)");
+  if (int rc = check_mala_pop_args("pita_ff_mala_pop", B, n_steps, dt_dev, totals, n_pop, pop_size, workspace)) return rc;
+  PITA_REQUIRE(ff->p.n >= 2, "pita_ff_mala_pop: needs at least two atoms");  // room for the populations in gs
+  if (B == 0 || n_steps == 0) return PITA_OK;  // as pita_ff_mala: an empty batch leaves dt_dev and rates_out untouched
+  PITA_REQUIRE(x && logp, "pita_ff_mala_pop: null argument (x, logp)");
+  MalaPopParams q = mala_pop_params(mala_params(noise, uniforms, walker_ids, seed, walker_offset, step0, 0, dt_dev, adaptive,
+                                                remove_mean, workspace), n_steps, totals, n_pop, pop_size, pop_base);
+  return ff_mala_chain(ff, x, logp, B, n_steps, dt_dev, rates_out, q, stream);
 }

@@ -367,9 +367,11 @@ __global__ void __launch_bounds__(256) ring_descent_kernel(float* __restrict__ x
 // the chain, groups outside, steps inside: a wave keeps its walkers on chip for all steps of the launch.  As in
 // lj13_mala_kernel there is no grid-wide barrier and no wait: a non-adaptive chain is one launch, an adaptive chain one
 // launch per step, each deriving its step size from dt_dev[0] and the counts of the steps before it (mala_replay_dt).
-template <int N, int DIM, int KIND, bool UNIT_RM>
+// POP (pita_lj_mala_pop, pita_dw_mala_pop): a walker's step size is its population's (MalaPopParams, pair_common.h), and
+// the counts are kept per (step of the launch, population).
+template <int N, int DIM, int KIND, bool UNIT_RM, bool POP = false>
 __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, float* __restrict__ logp, long long B,
-                                                        PairParams p, MalaParams q) {
+                                                        PairParams p, MalaQ<POP> q) {
   using R = Ring<N, DIM>;
   // the accept counters and seq_sums' shadow-lane handling below are written for the quad and the whole-wave mappings;
   // the DPP-row mapping (13 particles on 16 lanes) is validated for the energy kernel only
@@ -377,10 +379,22 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
   extern __shared__ __attribute__((aligned(16))) float sm[];
   // accepted walkers per block and step in LDS, flushed once at the end (a global atomic per wave and step -- 32 768 x
   // nsteps adds on nsteps addresses for LJ55 -- serialises in the L2 and costs more than the chain)
-  constexpr int STEP_CNT = 512;
+  // POP: the LDS stage holds the launch's own steps, [steps][n_pop] (an adaptive launch has one step, so n_pop entries);
+  // its budget is 2 048 counters = 8 KiB, which leaves eight blocks per CU their LDS next to the walker tables.  A launch
+  // with more (steps x populations) adds to global memory per wave and step instead.
+  constexpr int STEP_CNT = POP ? 2048 : 512;
   __shared__ int stepcnt[STEP_CNT];
-  const int cnt_end = q.step_base + q.steps < STEP_CNT ? q.step_base + q.steps : STEP_CNT;  // chain steps counted in LDS
-  for (int t = q.step_base + threadIdx.x; t < cnt_end; t += 256) stepcnt[t] = 0;
+  int cnt_lo, cnt_end;  // slots [cnt_lo, cnt_end) of stepcnt are this launch's
+  bool cnt_lds = true;
+  if constexpr (POP) {
+    cnt_lds = (long long)q.steps * q.n_pop <= STEP_CNT;
+    cnt_lo = 0;
+    cnt_end = cnt_lds ? q.steps * q.n_pop : 0;
+  } else {
+    cnt_lo = q.step_base;
+    cnt_end = q.step_base + q.steps < STEP_CNT ? q.step_base + q.steps : STEP_CNT;  // chain steps counted in LDS
+  }
+  for (int t = cnt_lo + threadIdx.x; t < cnt_end; t += 256) stepcnt[t] = 0;
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float* tab1 = sm + wave * 2 * R::TAB_F;  // current walkers; pad slot of an entry: this particle's |x' - fwd mean|^2
@@ -388,10 +402,13 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
   const R r(lane);
   const long long ngroups = (B + R::WPW - 1) / R::WPW, nwaves = (long long)gridDim.x * 4;
   const long long g0 = (long long)blockIdx.x * 4 + wave;
-  const double dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
+  double dt = 0.0;
+  if constexpr (!POP) dt = mala_replay_dt(q.dt_dev, q.sync, q.step_base, q.total, q.adaptive);
+  int pop = 0;
   float xi[DIM], lp = 0.f;
 
-  // one MALA step of the walker group in (xi, lp, tab1); returns the number of accepted walkers of this wave
+  // one MALA step of the walker group in (xi, lp, tab1); returns the number of accepted walkers of this wave (POP: adds
+  // them to their populations' counters and returns 0)
   auto step = [&](long long ws, bool act, int s) -> int {
     const float hdt = (float)(0.5 * dt), sdt = (float)sqrt(dt), tdt = (float)(2.0 * dt);
     float F[DIM], Fp[DIM], e, lpp = 0.f, dummy;
@@ -476,6 +493,14 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
     for (int k = 0; k < DIM; ++k) xi[k] = v[k];
     r.put(tab1, xi);
     wfence();
+    if constexpr (POP) {
+      mala_count_by_pop(act && r.i == 0, af != 0.f, pop, [&](int pl, int c) {
+        if (cnt_lds) atomicAdd(&stepcnt[(s - q.step_base) * q.n_pop + pl], c);
+        else __hip_atomic_fetch_add(&q.sync[(long long)s * q.n_pop + pl], (unsigned long long)c, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+      });
+      return 0;
+    }
     return __popcll(__ballot(act && r.i == 0 && af != 0.f));
   };
 
@@ -484,6 +509,10 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
     lp = logp[ws];
     r.put(tab1, xi);
     wfence();
+    if constexpr (POP) {
+      pop = mala_pop_of(q, q.walker_ids ? (unsigned long long)q.walker_ids[ws] : q.walker_offset + (unsigned long long)ws);
+      dt = mala_replay_dt(q, pop);
+    }
   };
   auto store = [&](long long w, bool act) {
     if (act) {
@@ -509,9 +538,11 @@ __global__ void __launch_bounds__(256) ring_mala_kernel(float* __restrict__ x, f
     store(w, act);
   }
   __syncthreads();
-  for (int t = q.step_base + threadIdx.x; t < cnt_end; t += 256)
+  long long cnt_at = 0;  // stepcnt[0]'s counter in q.sync
+  if constexpr (POP) cnt_at = (long long)q.step_base * q.n_pop;
+  for (int t = cnt_lo + threadIdx.x; t < cnt_end; t += 256)
     if (stepcnt[t])
-      __hip_atomic_fetch_add(&q.sync[t], (unsigned long long)stepcnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&q.sync[cnt_at + t], (unsigned long long)stepcnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Persistent grids: exactly one residency of the kernel (resident blocks per CU x CUs; a performance choice -- no tail
@@ -551,10 +582,11 @@ struct RingLaunch {
       return (int)PITA_OK;
     });
   }
-  static int mala(float* x, float* logp, long long B, const PairParams& p, const MalaParams& q, hipStream_t s) {
+  template <class Q>
+  static int mala(float* x, float* logp, long long B, const PairParams& p, const Q& q, hipStream_t s) {
     const size_t lds = sizeof(float) * 4 * 2 * R::TAB_F;
     return dispatch_bool(unit_rm(p), [&](auto unit) {
-      auto* kernel = ring_mala_kernel<N, DIM, KIND, decltype(unit)::value>;
+      auto* kernel = ring_mala_kernel<N, DIM, KIND, decltype(unit)::value, std::is_same<Q, MalaPopParams>::value>;
       unsigned grid = 0;
       if (int rc = grid_for(kernel, lds, B, grid)) return rc;
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, x, logp, B, p, q);
@@ -581,11 +613,20 @@ int ring_launch_descent(int kind, float* x, const float* noise, int64_t B, int n
   return 1;
 }
 
-int ring_launch_mala(int kind, float* x, float* logp, int64_t B, int n, int d, const PairParams& p, MalaParams q,
-                     void* stream) {
+template <class Q>
+static int ring_mala_for(int kind, float* x, float* logp, int64_t B, int n, int d, const PairParams& p, const Q& q,
+                         void* stream) {
   if (kind == E_LJ && n == 55 && d == 3) return RingLaunch<55, 3, E_LJ>::mala(x, logp, B, p, q, (hipStream_t)stream);
   if (kind == E_DW && n == 4 && d == 2) return RingLaunch<4, 2, E_DW>::mala(x, logp, B, p, q, (hipStream_t)stream);
   return 1;
+}
+int ring_launch_mala(int kind, float* x, float* logp, int64_t B, int n, int d, const PairParams& p, MalaParams q,
+                     void* stream) {
+  return ring_mala_for(kind, x, logp, B, n, d, p, q, stream);
+}
+int ring_launch_mala(int kind, float* x, float* logp, int64_t B, int n, int d, const PairParams& p, MalaPopParams q,
+                     void* stream) {
+  return ring_mala_for(kind, x, logp, B, n, d, p, q, stream);
 }
 
 }  // namespace pita

@@ -179,17 +179,34 @@ __global__ void __launch_bounds__(256) edm_combine_kernel(const float* __restric
 // ---------------------------------------------------------------------------- MALA
 // The step size lives on the device (double, like the Python float it replaces) so the adaptive chain
 // runs without a host round trip per step; the kernels round it to fp32 where torch would.
-template <int DIM>
+// The per-population chain (pita_mala_*_pop) instantiates the kernels with one trailing PopKeys argument: dt_dev and
+// acc_count are then [n_pop] and every walker reads and counts in the entry of its own population.
+struct PopKeys {
+  unsigned long long base;  // population of the walker with Philox key k: (k - base) / size
+  long long size;
+  __device__ __forceinline__ int of(unsigned long long key) const { return (int)((key - base) / (unsigned long long)size); }
+};
+template <class T>
+__device__ __forceinline__ const T& only(const T& t) { return t; }
+
+template <int DIM, class... Pop>
 __global__ void __launch_bounds__(256) mala_propose_kernel(const float* __restrict__ x, const float* __restrict__ force,
                                                            float* __restrict__ x_prop, const float* __restrict__ noise,
                                                            long long B, int n, const double* __restrict__ dt_dev,
-                                                           ElemParams p) {
-  const float hdt = (float)(0.5 * dt_dev[0]), sdt = (float)sqrt(dt_dev[0]);
+                                                           ElemParams p, Pop... pk) {
+  constexpr bool POP = sizeof...(Pop) != 0;
+  float hdt = 0.f, sdt = 0.f;
+  if constexpr (!POP) { hdt = (float)(0.5 * dt_dev[0]); sdt = (float)sqrt(dt_dev[0]); }
   const long long total = B * n;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
     const long long w = t / n;
     const int i = (int)(t - w * n);
     const long long base = t * DIM;
+    if constexpr (POP) {
+      const double dt = dt_dev[only(pk...).of(p.walker_ids ? (unsigned long long)p.walker_ids[w]
+                                                           : p.walker_offset + (unsigned long long)w)];
+      hdt = (float)(0.5 * dt); sdt = (float)sqrt(dt);
+    }
     float xi[4] = {0.f, 0.f, 0.f, 0.f};
     if (noise) {
 #pragma unroll
@@ -203,20 +220,23 @@ __global__ void __launch_bounds__(256) mala_propose_kernel(const float* __restri
   }
 }
 
-template <int DIM>
+template <int DIM, class... Pop>
 __global__ void __launch_bounds__(256) mala_accept_kernel(float* __restrict__ x, float* __restrict__ logp,
                                                           const float* __restrict__ force, const float* __restrict__ x_prop,
                                                           const float* __restrict__ logp_prop,
                                                           const float* __restrict__ force_prop,
                                                           const float* __restrict__ uniforms, long long B, int n, int WB,
                                                           const double* __restrict__ dt_dev, int* __restrict__ acc_count,
-                                                          ElemParams p) {
+                                                          ElemParams p, Pop... pk) {
+  constexpr bool POP = sizeof...(Pop) != 0;
   extern __shared__ float sm[];
   float* xsel = sm;                      // [WB*n*DIM] accepted/kept coordinates
   float* qf = sm + WB * n * DIM;         // [WB*n] partial |x' - fwd_mean|^2
   float* qb = qf + WB * n;               // [WB*n] partial |x - bwd_mean|^2
   float* flag = qb + WB * n;             // [WB]   1.0 = accepted
-  const float hdt = (float)(0.5 * dt_dev[0]), tdt = (float)(2.0 * dt_dev[0]);
+  int* popl = reinterpret_cast<int*>(flag + WB);  // POP: [WB] population of the block's walkers
+  float hdt = 0.f, tdt = 0.f;
+  if constexpr (!POP) { hdt = (float)(0.5 * dt_dev[0]); tdt = (float)(2.0 * dt_dev[0]); }
   const int tid = threadIdx.x;
   const long long nblk = (B + WB - 1) / WB;
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -226,6 +246,15 @@ __global__ void __launch_bounds__(256) mala_accept_kernel(float* __restrict__ x,
     const bool act = w < nw;
     const long long base = ((w0 + w) * n + i) * DIM;
     float xo[DIM], xp[DIM];
+    if constexpr (POP) {
+      if (act) {
+        const int pop = only(pk...).of(p.walker_ids ? (unsigned long long)p.walker_ids[w0 + w]
+                                                    : p.walker_offset + (unsigned long long)(w0 + w));
+        const double dt = dt_dev[pop];
+        hdt = (float)(0.5 * dt); tdt = (float)(2.0 * dt);
+        if (i == 0) popl[w] = pop;
+      }
+    }
     if (act) {
       float sf = 0.f, sb = 0.f;
 #pragma unroll
@@ -267,8 +296,18 @@ __global__ void __launch_bounds__(256) mala_accept_kernel(float* __restrict__ x,
     }
     if (tid == 0) {
       int c = 0;
-      for (int j = 0; j < nw; ++j) c += flag[j] != 0.f;
-      if (c) atomicAdd(acc_count, c);
+      if constexpr (POP) {  // a block's walkers can straddle populations: one add per run of equal populations
+        for (int j = 0; j < nw; ++j) {
+          c += flag[j] != 0.f;
+          if (c && (j + 1 == nw || popl[j + 1] != popl[j])) {
+            atomicAdd(&acc_count[popl[j]], c);
+            c = 0;
+          }
+        }
+      } else {
+        for (int j = 0; j < nw; ++j) c += flag[j] != 0.f;
+        if (c) atomicAdd(acc_count, c);
+      }
     }
     __syncthreads();
     if (act) {
@@ -291,6 +330,18 @@ __global__ void mala_adapt_kernel(double* dt_dev, int* acc_count, long long tota
   if (rate_out) rate_out[0] = rate;
   if (adaptive) dt_dev[0] = ((double)rate > 0.55) ? dt_dev[0] * 1.1 : dt_dev[0] / 1.1;  // sde_integration.py:439-443
   acc_count[0] = 0;
+}
+
+// the rule of mala_adapt_kernel for every population, one thread each; a population without walkers keeps its step size
+__global__ void __launch_bounds__(64) mala_adapt_pop_kernel(double* dt_dev, int* acc_count, const long long* totals,
+                                                            int n_pop, int adaptive, float* rate_out) {
+  const int pop = blockIdx.x * 64 + threadIdx.x;
+  if (pop >= n_pop) return;
+  const long long total = totals[pop];
+  const float rate = total > 0 ? (float)acc_count[pop] / (float)total : NAN;
+  if (rate_out) rate_out[pop] = rate;
+  if (adaptive && total > 0) dt_dev[pop] = ((double)rate > 0.55) ? dt_dev[pop] * 1.1 : dt_dev[pop] / 1.1;
+  acc_count[pop] = 0;
 }
 
 // ---------------------------------------------------------------------------- resampling
@@ -949,6 +1000,22 @@ extern "C" int pita_gather_rows(const float* src, const int64_t* ids, float* out
   return PITA_OK;
 }
 
+// the launches of pita_mala_propose (no pk) and pita_mala_propose_pop (pk: one PopKeys)
+template <class... Pop>
+static int launch_mala_propose(const float* x, const float* force, float* x_prop, const float* noise, int64_t B, int n, int d,
+                               const double* dt_dev, const ElemParams& p, void* stream, Pop... pk) {
+  const long long nb = (B * n + 255) / 256;
+  const unsigned grid = (unsigned)(nb < 8192 ? nb : 8192);
+  hipStream_t s = (hipStream_t)stream;
+  switch (d) {
+    case 1: hipLaunchKernelGGL((mala_propose_kernel<1, Pop...>), dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p, pk...); break;
+    case 2: hipLaunchKernelGGL((mala_propose_kernel<2, Pop...>), dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p, pk...); break;
+    default: hipLaunchKernelGGL((mala_propose_kernel<3, Pop...>), dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p, pk...); break;
+  }
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
 extern "C" int pita_mala_propose(const float* x, const float* force, float* x_prop, const float* noise, int64_t B, int n,
                                  int d, const double* dt_dev, uint64_t seed, uint64_t walker_offset,
                                  const int64_t* walker_ids, int64_t step, void* stream) {
@@ -958,13 +1025,38 @@ extern "C" int pita_mala_propose(const float* x, const float* force, float* x_pr
   PITA_REQUIRE(n >= 1 && n <= 256 && d >= 1 && d <= 3, "pita_mala_propose: n_particles in [1,256], n_dim in [1,3]");
   ElemParams p{};
   p.seed = seed; p.walker_offset = walker_offset; p.step = step; p.walker_ids = (const long long*)walker_ids;
-  const long long nb = (B * n + 255) / 256;
-  const unsigned grid = (unsigned)(nb < 8192 ? nb : 8192);
+  return launch_mala_propose(x, force, x_prop, noise, B, n, d, dt_dev, p, stream);
+}
+
+extern "C" int pita_mala_propose_pop(const float* x, const float* force, float* x_prop, const float* noise, int64_t B, int n,
+                                     int d, const double* dt_dev, int n_pop, int64_t pop_size, uint64_t pop_base,
+                                     uint64_t seed, uint64_t walker_offset, const int64_t* walker_ids, int64_t step,
+                                     void* stream) {
+  PITA_REQUIRE(B >= 0, "pita_mala_propose_pop: negative batch");
+  PITA_REQUIRE(dt_dev, "pita_mala_propose_pop: null argument (dt_dev)");
+  PITA_REQUIRE(n_pop >= 1 && pop_size >= 1, "pita_mala_propose_pop: bad argument (n_pop >= 1, pop_size >= 1)");
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(x && force && x_prop, "pita_mala_propose_pop: null argument");
+  PITA_REQUIRE(n >= 1 && n <= 256 && d >= 1 && d <= 3, "pita_mala_propose_pop: n_particles in [1,256], n_dim in [1,3]");
+  ElemParams p{};
+  p.seed = seed; p.walker_offset = walker_offset; p.step = step; p.walker_ids = (const long long*)walker_ids;
+  return launch_mala_propose(x, force, x_prop, noise, B, n, d, dt_dev, p, stream, PopKeys{pop_base, (long long)pop_size});
+}
+
+// the launches of pita_mala_accept (no pk) and pita_mala_accept_pop (pk: one PopKeys, and WB more LDS words for popl)
+template <class... Pop>
+static int launch_mala_accept(float* x, float* logp, const float* force, const float* x_prop, const float* logp_prop,
+                              const float* force_prop, const float* uniforms, int64_t B, int n, int d, const double* dt_dev,
+                              int* acc_count, const ElemParams& p, void* stream, Pop... pk) {
+  const int WB = 256 / n;
+  const long long nblk = (B + WB - 1) / WB;
+  const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
+  const size_t lds = sizeof(float) * (size_t)(WB * n * d + 2 * WB * n + WB + (sizeof...(Pop) ? WB : 0));
   hipStream_t s = (hipStream_t)stream;
   switch (d) {
-    case 1: hipLaunchKernelGGL(mala_propose_kernel<1>, dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p); break;
-    case 2: hipLaunchKernelGGL(mala_propose_kernel<2>, dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p); break;
-    default: hipLaunchKernelGGL(mala_propose_kernel<3>, dim3(grid), dim3(256), 0, s, x, force, x_prop, noise, B, n, dt_dev, p); break;
+    case 1: hipLaunchKernelGGL((mala_accept_kernel<1, Pop...>), dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p, pk...); break;
+    case 2: hipLaunchKernelGGL((mala_accept_kernel<2, Pop...>), dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p, pk...); break;
+    default: hipLaunchKernelGGL((mala_accept_kernel<3, Pop...>), dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p, pk...); break;
   }
   PITA_LAUNCH_CHECK();
   return PITA_OK;
@@ -982,24 +1074,41 @@ extern "C" int pita_mala_accept(float* x, float* logp, const float* force, const
   ElemParams p{};
   p.seed = seed; p.walker_offset = walker_offset; p.step = step; p.remove_mean = remove_mean;
   p.walker_ids = (const long long*)walker_ids;
-  const int WB = 256 / n;
-  const long long nblk = (B + WB - 1) / WB;
-  const unsigned grid = (unsigned)(nblk < 256LL * 16 ? nblk : 256LL * 16);
-  const size_t lds = sizeof(float) * (size_t)(WB * n * d + 2 * WB * n + WB);
-  hipStream_t s = (hipStream_t)stream;
-  switch (d) {
-    case 1: hipLaunchKernelGGL(mala_accept_kernel<1>, dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p); break;
-    case 2: hipLaunchKernelGGL(mala_accept_kernel<2>, dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p); break;
-    default: hipLaunchKernelGGL(mala_accept_kernel<3>, dim3(grid), dim3(256), lds, s, x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, WB, dt_dev, acc_count, p); break;
-  }
-  PITA_LAUNCH_CHECK();
-  return PITA_OK;
+  return launch_mala_accept(x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, d, dt_dev, acc_count, p, stream);
+}
+
+extern "C" int pita_mala_accept_pop(float* x, float* logp, const float* force, const float* x_prop, const float* logp_prop,
+                                    const float* force_prop, const float* uniforms, int64_t B, int n, int d,
+                                    const double* dt_dev, int n_pop, int64_t pop_size, uint64_t pop_base, uint64_t seed,
+                                    uint64_t walker_offset, const int64_t* walker_ids, int64_t step, int remove_mean,
+                                    int* acc_count, void* stream) {
+  PITA_REQUIRE(B >= 0, "pita_mala_accept_pop: negative batch");
+  PITA_REQUIRE(dt_dev && acc_count, "pita_mala_accept_pop: null argument (dt_dev, acc_count)");
+  PITA_REQUIRE(n_pop >= 1 && pop_size >= 1, "pita_mala_accept_pop: bad argument (n_pop >= 1, pop_size >= 1)");
+  if (B == 0) return PITA_OK;
+  PITA_REQUIRE(x && logp && force && x_prop && logp_prop && force_prop, "pita_mala_accept_pop: null argument");
+  PITA_REQUIRE(n >= 1 && n <= 256 && d >= 1 && d <= 3, "pita_mala_accept_pop: n_particles in [1,256], n_dim in [1,3]");
+  ElemParams p{};
+  p.seed = seed; p.walker_offset = walker_offset; p.step = step; p.remove_mean = remove_mean;
+  p.walker_ids = (const long long*)walker_ids;
+  return launch_mala_accept(x, logp, force, x_prop, logp_prop, force_prop, uniforms, B, n, d, dt_dev, acc_count, p, stream,
+                            PopKeys{pop_base, (long long)pop_size});
 }
 
 extern "C" int pita_mala_adapt(double* dt_dev, int* acc_count, int64_t total, int adaptive, float* rate_out, void* stream) {
   PITA_REQUIRE(dt_dev && acc_count && total > 0, "pita_mala_adapt: bad argument");
   hipLaunchKernelGGL(mala_adapt_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dt_dev, acc_count, (long long)total,
                      adaptive, rate_out);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+extern "C" int pita_mala_adapt_pop(double* dt_dev, int* acc_count, const int64_t* totals, int n_pop, int adaptive,
+                                   float* rate_out, void* stream) {
+  PITA_REQUIRE(dt_dev && acc_count && totals, "pita_mala_adapt_pop: null argument (dt_dev, acc_count, totals)");
+  PITA_REQUIRE(n_pop >= 1, "pita_mala_adapt_pop: bad argument (n_pop >= 1)");
+  hipLaunchKernelGGL(mala_adapt_pop_kernel, dim3((unsigned)((n_pop + 63) / 64)), dim3(64), 0, (hipStream_t)stream, dt_dev,
+                     acc_count, (const long long*)totals, n_pop, adaptive, rate_out);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

@@ -38,6 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._target import MalaPopulations
 from .data_utils import remove_mean
 from .metrics import logweight_stats
 from .sdes import SDETerms, TermStats, VEReverseSDE  # noqa: F401
@@ -436,6 +437,17 @@ _Run = collections.namedtuple("_Run", "comm off Bl Bg n d mean_free key noise ti
                                       "did_resampling model policy mala_draws")
 
 
+def _pooled_rates(stats):
+    """One acceptance rate per step from per-population ones: sum_p rate_p n_p / sum_p n_p in float64 over the
+    populations with valid walkers (``acceptance_rate`` [steps, P], ``n_valid`` [P]); NaN where there is none."""
+    nv = stats["n_valid"].astype(np.float64)
+    has = nv > 0
+    if not has.any():
+        return [float("nan")] * stats["acceptance_rate"].shape[0]
+    r = stats["acceptance_rate"].astype(np.float64)[:, has]
+    return ((r * nv[has]).sum(1) / nv[has].sum()).tolist()
+
+
 def _terms_from_stats(st4, st8, n_elem, n_walk, computed, debiased):
     """N light SDETerms from the per-step moment buffers (host copies happen once, here).  st4: [N, 4] drift_X /
     diffusion moments; st8: [N, 8] drift_A, divergence_score, cross_term, dUt_dt moments (debiased regime only)."""
@@ -461,7 +473,7 @@ class WeightedSDEIntegrator:
                  resampling_interval=-1, num_negative_time_steps=100, post_mcmc_steps=100, adaptive_mcmc=False,
                  batch_size=None, no_grad=True, resample_at_end=False, dt_negative_time=1e-4, do_langevin=False,
                  should_mean_free=True, seed=0, record_terms=False, verbose=False, ess_threshold=None,
-                 populations=None):
+                 populations=None, mcmc_per_population=False):
         """``ess_threshold``: None (the reference's fixed schedule: every due event resamples) or a fraction in [0, 1] --
         a due event then resamples only when the effective sample size of the log-weights is at most
         ``ess_threshold * batch``, decided on the device (``sample_cat_sys_adaptive``; an extension the reference does
@@ -474,13 +486,27 @@ class WeightedSDEIntegrator:
         (``sample_cat_sys_populations``) plus the row gather on the rank's own walkers, with no collective, because
         populations never straddle ranks.  ``resample_u`` is then [events, P] (event-major, ``resample_at_end`` last),
         ``last_weight_stats`` is filled whatever ``ess_threshold`` is, its per-event arrays are [N, P] and ``log_z`` is
-        [P].  The one coupling between populations: an adaptive MALA step size adapts to the acceptance rate over the
-        whole batch."""
+        [P].  The one coupling between populations is the post-processing MALA chain of ``adaptive_mcmc=True``: its one
+        step size adapts to the acceptance rate over the whole batch -- unless ``mcmc_per_population`` is set.
+
+        ``mcmc_per_population``: False (the chain as above) or True, which needs ``populations`` -- every population
+        then has its own MALA step size, acceptance count and adaptation, so what a population returns depends on its own
+        walkers alone, bit for bit.  The chain is rank-local (no all-reduce, the fused route whatever the world size).
+        ``acceptance_rate_list`` stays one float per step: sum_p rate_p n_p / sum_p n_p in float64 over the populations
+        with walkers (n_p: walkers of population p with a finite target log-density), and ``last_mcmc_stats`` holds
+        ``acceptance_rate`` (float32 [steps, P], NaN for a population without such walkers), ``step_size`` (float64
+        [P], final) and ``n_valid`` (int64 [P]) of the last run; it is None without the mode."""
         if populations is not None:
             if isinstance(populations, bool) or not isinstance(populations, (int, np.integer)) or populations < 1:
                 raise ValueError(f"populations must be None or an int >= 1, got {populations!r}")
             populations = int(populations)
         self.populations = populations
+        if not isinstance(mcmc_per_population, (bool, np.bool_)):
+            raise ValueError(f"mcmc_per_population must be a bool, got {mcmc_per_population!r}")
+        if mcmc_per_population and populations is None:
+            raise ValueError("mcmc_per_population=True needs populations: without them there is one chain over the batch")
+        self.mcmc_per_population = bool(mcmc_per_population)
+        self.last_mcmc_stats = None
         if ess_threshold is not None:
             try:
                 ok = 0.0 <= float(ess_threshold) <= 1.0  # NaN fails both comparisons
@@ -643,11 +669,20 @@ class WeightedSDEIntegrator:
             x = self.negative_time_descent(x, run.target, walker_offset=run.off)
         keep_order = run.policy.keep_order
         acceptance_rate_list = []
+        self.last_mcmc_stats = None
         if self.post_mcmc_steps > 0:
             fn = self.metropolis_hastings_mala_adaptive if self.adaptive_mcmc else self.metropolis_hastings_mala
             kw = dict(dt_init=self.dt_negative_time) if self.adaptive_mcmc else {}
-            x, acceptance_rate_list = fn(x, run.target, return_acceptance_rate=True, walker_offset=run.off, comm=run.comm,
-                                         noise=run.mala_draws[0], uniforms=run.mala_draws[1], keep_order=keep_order, **kw)
+            if self.mcmc_per_population:
+                # the rates come from every rank's populations: one gather after the chain, then the pooled rate per step
+                x, _ = fn(x, run.target, walker_offset=run.off, noise=run.mala_draws[0], uniforms=run.mala_draws[1],
+                          keep_order=keep_order, pop_size=run.policy.S, **kw)
+                self.last_mcmc_stats = self._gather_mcmc_stats(run.policy)
+                acceptance_rate_list = _pooled_rates(self.last_mcmc_stats)
+            else:
+                x, acceptance_rate_list = fn(x, run.target, return_acceptance_rate=True, walker_offset=run.off,
+                                             comm=run.comm, noise=run.mala_draws[0], uniforms=run.mala_draws[1],
+                                             keep_order=keep_order, **kw)
         # X1: the only collective on the resampling-free path
         return self._gather_final(x, run.comm, run.Bl, keep_order), acceptance_rate_list
 
@@ -796,35 +831,35 @@ class WeightedSDEIntegrator:
                        "pita_em_step")
         return x
 
+    def _gather_mcmc_stats(self, policy):
+        """``last_mcmc_stats`` from what the per-population chain left on this rank (``_mala_pop_state``): one gather in
+        ``_PopulationEvents.gather``'s layout and one host copy."""
+        rates, dt_dev, totals = self._mala_pop_state
+        packed = torch.cat([rates.double(), dt_dev[None], totals[None].double()])  # [steps + 2, Pl]; float32 and counts are exact
+        h = policy.gather(packed).cpu().numpy()
+        return {"acceptance_rate": h[:-2].astype(np.float32), "step_size": h[-2].copy(), "n_valid": h[-1].astype(np.int64)}
+
     def _mala(self, x, energy_function, adaptive, dt, noise=None, uniforms=None, return_acceptance_rate=False,
-              walker_offset=0, comm=None, fused=True, keep_order=False):
+              walker_offset=0, comm=None, fused=True, keep_order=False, pop_size=None):
         """MALA with the reference's finite-mask semantics (:362-470): non-finite-logp walkers are set aside and
         re-appended AFTER the valid ones (order not preserved, quirk Q7).  Proposal, accept/reject and the step-size
         adaptation run as HIP kernels with the step size on the device: no host synchronisation inside the chain (the
         acceptance rates are copied to the host afterwards, and only when the caller asks for them).
         With several ranks the acceptance count is all-reduced so the adaptation sees the global rate, as the
         reference (which runs the chain on the gathered batch on every rank) does.  ``keep_order`` (runs with
-        ``populations``): the set-aside walkers go back to their own rows instead."""
+        ``populations``): the set-aside walkers go back to their own rows instead.
+        ``pop_size`` (``mcmc_per_population``): the rows are populations of ``pop_size`` walkers, the first of them at
+        Philox key ``walker_offset``, each with its own step size, count and adaptation (the ``_pop`` kernels on either
+        route); the chain is rank-local, ``comm`` is not used.  Its per-population rates [steps, Pl], final step sizes
+        [Pl] and valid-walker counts [Pl] stay on the device in ``_mala_pop_state``; the rate returned per step is the
+        pooled one, sum_p rate_p n_p / sum_p n_p in float64 over the populations with valid walkers."""
+        if pop_size is not None:
+            return self._mala_populations(x, energy_function, adaptive, dt, int(pop_size), noise, uniforms,
+                                          return_acceptance_rate, int(walker_offset), fused, keep_order)
         n, d = self._geometry(x, energy_function)
         L = _lib.lib()
-        x = _lib.dev_tensor(x, "x")
-
-        def join(x_valid, x_invalid):
-            if not keep_order:
-                return torch.cat([x_valid, x_invalid], dim=0)
-            out = x.clone()
-            out[valid] = x_valid
-            return out
-
-        dev = x.device
-        logp_all = energy_function(x)
-        valid = torch.isfinite(logp_all)
-        x_valid, x_invalid = x[valid].contiguous(), x[~valid]
-        logp = logp_all[valid].contiguous()
-        Bv = x_valid.shape[0]
-        # Philox keys follow the walkers' ORIGINAL global indices, not their position in the compacted batch
-        ids = (torch.nonzero(valid).reshape(-1) + int(walker_offset)).contiguous() if Bv < x.shape[0] else None
-        self._last_mala_valid = Bv
+        x, valid, x_valid, logp, ids = self._mala_split(x, energy_function, walker_offset)
+        dev, Bv = x.device, x_valid.shape[0]
         total = Bv
         world = comm.world if comm is not None and torch.distributed.is_initialized() else 1
         if world > 1:
@@ -838,27 +873,17 @@ class WeightedSDEIntegrator:
             dt_dev = torch.tensor([dt], device=dev, dtype=torch.float64)
             count = torch.zeros(1, device=dev, dtype=torch.int32)
             x_prop = torch.empty_like(x_valid)
-            key = self._key(2)
-            # :397-398 centres through maybe_remove_mean, the adaptive variant (:458-461) unconditionally
-            rm = int(bool(getattr(energy_function, "is_molecule", False)) and (adaptive or bool(self.should_mean_free)))
+            key, rm = self._key(2), self._mala_centres(energy_function, adaptive)
             st = _lib.stream_ptr(dev)
             # targets with a fused chain kernel: walkers on chip, one launch for a non-adaptive chain, one per step for
             # an adaptive one (bit-identical to the loop below); the global acceptance rate of several ranks needs the
             # per-step all-reduce below
             if fused and world == 1 and Bv > 0 and hasattr(energy_function, "fused_mala"):
-                nz = uu = None
-                if noise is not None:
-                    nz = torch.stack([_lib.dev_tensor(noise[i], "noise") for i in range(steps)]).contiguous()
-                    if tuple(nz.shape) != (steps,) + tuple(x_valid.shape):
-                        raise ValueError(f"MALA noise has shape {tuple(nz.shape)}, expected {(steps,) + tuple(x_valid.shape)}")
-                if uniforms is not None:
-                    uu = torch.stack([_lib.dev_tensor(uniforms[i], "uniforms").reshape(-1) for i in range(steps)]).contiguous()
-                    if tuple(uu.shape) != (steps, Bv):
-                        raise ValueError(f"MALA uniforms have shape {tuple(uu.shape)}, expected {(steps, Bv)}")
+                nz, uu = self._mala_draws(noise, uniforms, steps, x_valid)
                 if energy_function.fused_mala(x_valid, logp, steps, dt_dev, adaptive, total, noise=nz, uniforms=uu, seed=key,
                                               walker_offset=walker_offset, walker_ids=ids, step0=0, remove_mean=rm,
                                               rates_out=rates) is not None:
-                    out = join(x_valid, x_invalid)
+                    out = self._mala_join(x, valid, x_valid, keep_order)
                     return (out, rates[:steps].tolist()) if return_acceptance_rate else (out, None)
             for i in range(steps):
                 if Bv > 0:
@@ -883,15 +908,103 @@ class WeightedSDEIntegrator:
                 _lib.check(L.pita_mala_adapt(dt_dev.data_ptr(), count.data_ptr(), total, int(adaptive),
                                              rates[i:].data_ptr(), st), "pita_mala_adapt")
                 done += 1
-        out = join(x_valid, x_invalid)
+        out = self._mala_join(x, valid, x_valid, keep_order)
         return (out, rates[:done].tolist()) if return_acceptance_rate else (out, None)
 
+    # what the two chains share: the split into valid and set-aside walkers, the centring rule, the injected draws of a
+    # fused chain, and the way back to one batch
+    def _mala_split(self, x, energy_function, walker_offset):
+        """``(x, valid, x_valid, logp, ids)``: the finite mask of the target log-density, the compacted walkers and their
+        log-densities, and their Philox keys (None when no walker is set aside)."""
+        x = _lib.dev_tensor(x, "x")
+        logp_all = energy_function(x)
+        valid = torch.isfinite(logp_all)
+        x_valid = x[valid].contiguous()
+        logp = logp_all[valid].contiguous()
+        Bv = x_valid.shape[0]
+        # Philox keys follow the walkers' ORIGINAL global indices, not their position in the compacted batch
+        ids = (torch.nonzero(valid).reshape(-1) + int(walker_offset)).contiguous() if Bv < x.shape[0] else None
+        self._last_mala_valid = Bv
+        return x, valid, x_valid, logp, ids
+
+    def _mala_centres(self, energy_function, adaptive):
+        # :397-398 centres through maybe_remove_mean, the adaptive variant (:458-461) unconditionally
+        return int(bool(getattr(energy_function, "is_molecule", False)) and (adaptive or bool(self.should_mean_free)))
+
+    @staticmethod
+    def _mala_draws(noise, uniforms, steps, x_valid):
+        """Injected normals [steps, Bv, D] and uniforms [steps, Bv] of a whole chain, stacked and checked (None: Philox)."""
+        nz = uu = None
+        if noise is not None:
+            nz = torch.stack([_lib.dev_tensor(noise[i], "noise") for i in range(steps)]).contiguous()
+            if tuple(nz.shape) != (steps,) + tuple(x_valid.shape):
+                raise ValueError(f"MALA noise has shape {tuple(nz.shape)}, expected {(steps,) + tuple(x_valid.shape)}")
+        if uniforms is not None:
+            uu = torch.stack([_lib.dev_tensor(uniforms[i], "uniforms").reshape(-1) for i in range(steps)]).contiguous()
+            if tuple(uu.shape) != (steps, x_valid.shape[0]):
+                raise ValueError(f"MALA uniforms have shape {tuple(uu.shape)}, expected {(steps, x_valid.shape[0])}")
+        return nz, uu
+
+    @staticmethod
+    def _mala_join(x, valid, x_valid, keep_order):
+        """The batch after the chain: [valid, set-aside] (quirk Q7), or every walker in its own row."""
+        if not keep_order:
+            return torch.cat([x_valid, x[~valid]], dim=0)
+        out = x.clone()
+        out[valid] = x_valid
+        return out
+
+    def _mala_populations(self, x, energy_function, adaptive, dt, S, noise, uniforms, return_acceptance_rate,
+                          walker_offset, fused, keep_order):
+        """``_mala`` with ``pop_size=S``: the same chain, step for step, with the per-population kernels."""
+        n, d = self._geometry(x, energy_function)
+        L = _lib.lib()
+        if S < 1 or x.shape[0] % S != 0:
+            raise ValueError(f"{x.shape[0]} walkers are no whole populations of {S}")
+        Pl = x.shape[0] // S
+        x, valid, x_valid, logp, ids = self._mala_split(x, energy_function, walker_offset)
+        dev, Bv = x.device, x_valid.shape[0]
+        totals = valid.reshape(Pl, S).sum(1)  # int64 [Pl], on the device: the bincount of the valid rows' populations
+        steps = int(self.post_mcmc_steps)
+        dt_dev = torch.full((Pl,), dt, device=dev, dtype=torch.float64)
+        rates = torch.full((max(steps, 0), Pl), float("nan"), device=dev)  # what a population without walkers keeps
+        if Bv > 0 and steps > 0:
+            pops = MalaPopulations(S, walker_offset, totals)
+            key, rm = self._key(2), self._mala_centres(energy_function, adaptive)
+            st = _lib.stream_ptr(dev)
+            nz, uu = self._mala_draws(noise, uniforms, steps, x_valid)
+            if not (fused and hasattr(energy_function, "fused_mala") and energy_function.fused_mala(
+                    x_valid, logp, steps, dt_dev, adaptive, pops, noise=nz, uniforms=uu, seed=key,
+                    walker_offset=walker_offset, walker_ids=ids, step0=0, remove_mean=rm, rates_out=rates) is not None):
+                count = torch.zeros(Pl, device=dev, dtype=torch.int32)
+                x_prop = torch.empty_like(x_valid)
+                for i in range(steps):
+                    _, grad = energy_function(x_valid, return_force=True)
+                    _lib.check(L.pita_mala_propose_pop(x_valid.data_ptr(), grad.data_ptr(), x_prop.data_ptr(),
+                                                       _lib.ptr(nz[i] if nz is not None else None), Bv, n, d,
+                                                       dt_dev.data_ptr(), Pl, S, walker_offset, key, walker_offset,
+                                                       _lib.ptr(ids), i, st), "pita_mala_propose_pop")
+                    logp_prop, grad_prop = energy_function(x_prop, return_force=True)
+                    _lib.check(L.pita_mala_accept_pop(x_valid.data_ptr(), logp.data_ptr(), grad.data_ptr(), x_prop.data_ptr(),
+                                                      logp_prop.data_ptr(), grad_prop.data_ptr(),
+                                                      _lib.ptr(uu[i] if uu is not None else None), Bv, n, d,
+                                                      dt_dev.data_ptr(), Pl, S, walker_offset, key, walker_offset,
+                                                      _lib.ptr(ids), i, rm, count.data_ptr(), st), "pita_mala_accept_pop")
+                    _lib.check(L.pita_mala_adapt_pop(dt_dev.data_ptr(), count.data_ptr(), totals.data_ptr(), Pl,
+                                                     int(adaptive), rates[i].data_ptr(), st), "pita_mala_adapt_pop")
+        self._mala_pop_state = (rates, dt_dev, totals)
+        out = self._mala_join(x, valid, x_valid, keep_order)
+        if not return_acceptance_rate:
+            return out, None
+        return out, _pooled_rates({"acceptance_rate": rates.cpu().numpy(), "n_valid": totals.cpu().numpy()})
+
     def metropolis_hastings_mala(self, x, energy_function, return_acceptance_rate=False, noise=None, uniforms=None,
-                                 walker_offset=0, comm=None, fused=True, keep_order=False):
+                                 walker_offset=0, comm=None, fused=True, keep_order=False, pop_size=None):
         return self._mala(x, energy_function, False, float(self.dt_negative_time), noise, uniforms,
-                          return_acceptance_rate, walker_offset, comm, fused, keep_order)
+                          return_acceptance_rate, walker_offset, comm, fused, keep_order, pop_size)
 
     def metropolis_hastings_mala_adaptive(self, x, energy_function, dt_init, return_acceptance_rate=False, noise=None,
-                                          uniforms=None, walker_offset=0, comm=None, fused=True, keep_order=False):
+                                          uniforms=None, walker_offset=0, comm=None, fused=True, keep_order=False,
+                                          pop_size=None):
         return self._mala(x, energy_function, True, float(dt_init), noise, uniforms, return_acceptance_rate,
-                          walker_offset, comm, fused, keep_order)
+                          walker_offset, comm, fused, keep_order, pop_size)
