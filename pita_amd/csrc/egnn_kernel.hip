@@ -332,12 +332,18 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_kernel(EgnnParams p) {
             if (NODE16) Ai *= F16_UNSCALE;
           }
           f32x16 agg = {0};
-          float xacc[DIM], pown[DIM], p0own[DIM];
+          // One squared distance per lane: the rank-2 k-step below takes `radial` from the lower lane half (hh == 0) and
+          // `edge_attr` from the upper one, so each half reads ONE geometry -- the lower the current positions, the upper
+          // the frozen input positions -- and runs one difference / sum-of-squares chain on it.  The lower half's chain is
+          // the coordinate update's `df` / `radial`; the upper half's `xacc` is meaningless and never read (posnext,
+          // drift_out and the moments are written by hh == 0 only).  -10 vector instructions and 2 LDS reads per edge,
+          // same bits: 103.0 -> 101.1 ms per 100 steps on one box (profiles/r19_sampler_edge_cuts_ab.txt)
+          const float* ptab = hh ? pos0 : poscur;
+          float xacc[DIM], pown[DIM];
 #pragma unroll
           for (int k = 0; k < DIM; ++k) {
             xacc[k] = 0.f;
-            pown[k] = poscur[col[T] * DIM + k];
-            p0own[k] = pos0[col[T] * DIM + k];
+            pown[k] = ptab[col[T] * DIM + k];
           }
           const int cbase = col[T] - nodei[T];
 
@@ -354,18 +360,16 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) egnn_kernel(EgnnParams p) {
             int j = nodei[T] + dd;
             j = (j >= N) ? j - N : j;
             const int cj = (col[T] < ncol) ? cbase + j : col[T];
-            // geometry (coord2radial :348-356; edge_attr :79)
-            float df[DIM], radial = 0.f, ea = 0.f;
+            // geometry (coord2radial :348-356; edge_attr :79): `radial` in the lower lane half, edge_attr in the upper
+            float df[DIM], radial = 0.f;
 #pragma unroll
             for (int k = 0; k < DIM; ++k) {
-              df[k] = pown[k] - poscur[cj * DIM + k];
+              df[k] = pown[k] - ptab[cj * DIM + k];
               radial = fmaf(df[k], df[k], radial);
-              const float e0 = p0own[k] - pos0[cj * DIM + k];
-              ea = fmaf(e0, e0, ea);
             }
             // edge MLP layer 1 (:232-237,:270-271): Wa h_i + Wb h_j + b1, then one k-step [w_r|w_e]·[radial;ea]
             f32x16 m = Ai + lds_vec16(PB + cj * PBS + hh * 16);
-            m = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, hh ? ea : radial, m, 0, 0, 0);
+            m = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, radial, m, 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
             if (PREC == 2) silu16_out(m); else silu16(m);
             __builtin_amdgcn_s_setprio(1);
