@@ -769,6 +769,26 @@ int pita_population_resample(const float* logits, int64_t n_pop, int64_t pop_siz
                              int64_t* ids, int64_t* n_unique, double* stats, int* resampled, float* logw_next,
                              void* workspace, void* stream);
 
+/* The same events for populations of ANY size (pop_size >= 1, no PITA_EUNSUPPORTED case): arguments, outputs and
+ * argument checks of pita_population_resample, and the same contract -- population p's stats row, resampled[p],
+ * n_unique[p], ids (global rows) and logw_next are, bit for bit, those of
+ *   pita_adaptive_resample(logits + p * pop_size, pop_size, u0_dev[p], theta, ...)
+ * on its slice, whatever n_pop and p are (systematic resampling of utils.py:111-120 per population).  Always the
+ * multi-block route, also for pop_size <= 2 048: one statistics block per population (the single-block summation order of
+ * pita_adaptive_resample, so the ESS bits and the decisions are its own) writes resampled[p]; the five passes of
+ * pita_systematic_resample follow over a (virtual block of 1 024 walkers, population) grid, every block testing its
+ * population's flag; the search pass writes global rows, the identity where the flag is clear, and logw_next; one block
+ * per population counts the runs (n_unique[p] = pop_size where it did not resample).  At most seven launches whatever
+ * n_pop is (six when n_unique is null), stream order only: no grid barrier, no atomics, no host read; blocks of different
+ * populations share nothing.  logw_next may be `logits`: every pass that reads logits for the bins precedes the search
+ * pass in stream order, which copies an element only onto its own index.
+ * workspace: 8-byte aligned device scratch of at least pita_population_resample_blocks_workspace_bytes bytes = n_pop
+ * copies of pita_systematic_resample's layout (n_pop * pita_resample_workspace_bytes(pop_size)). */
+size_t pita_population_resample_blocks_workspace_bytes(int64_t n_pop, int64_t pop_size);
+int pita_population_resample_blocks(const float* logits, int64_t n_pop, int64_t pop_size, const double* u0_dev, double theta,
+                                    int64_t* ids, int64_t* n_unique, double* stats, int* resampled, float* logw_next,
+                                    void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- weighted per-population observables
  * An extension: the reference's evaluation counts every walker once and treats the batch as one population.
  *

@@ -177,6 +177,9 @@ _PROTOS = {
     "pita_population_resample_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "pita_population_resample": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pita_population_resample_blocks_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "pita_population_resample_blocks": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_double, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pita_weighted_histogram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
     "pita_pair_distance_histogram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,

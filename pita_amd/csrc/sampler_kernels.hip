@@ -742,6 +742,96 @@ __global__ void __launch_bounds__(1024) count_runs_gated_kernel(const int* __res
   }
 }
 
+// ---- populations of any size: P independent events of S walkers each through the SAME passes, over a (virtual block,
+// population) grid.  pop_stats_kernel (one block per population: the single-block summation order of the one-population
+// event, hence its ESS bits and decision) writes the P flags; every later block tests the flag of its population and runs
+// rs_*_block on the population's slice of the logits and its own copy of the scratch, so population p's bits are those of
+// pita_adaptive_resample on its slice, whatever P and p are.  Blocks of different populations share nothing; stream order
+// is the only synchronisation.  Populations beyond gridDim.y are reached by striding; the barrier that ends a round keeps
+// the next population's pass off the LDS the last one is still reading.
+struct RsScratch {
+  float *bins, *bmax;
+  double *bsum, *bw;
+};
+__host__ __device__ inline size_t rs_scratch_bytes(long long B, long long nb) {
+  return (((size_t)B * 4 + 7) & ~(size_t)7) + (((size_t)nb * 4 + 7) & ~(size_t)7) + 2 * (size_t)nb * 8;
+}
+// float bins[B] | float bmax[nb] | double bsum[nb] | double bw[nb]   (8-byte aligned sections)
+__host__ __device__ inline RsScratch rs_scratch(void* workspace, long long B, long long nb) {
+  char* w = static_cast<char*>(workspace);
+  RsScratch r;
+  r.bins = reinterpret_cast<float*>(w);
+  w += ((size_t)B * 4 + 7) & ~(size_t)7;
+  r.bmax = reinterpret_cast<float*>(w);
+  w += ((size_t)nb * 4 + 7) & ~(size_t)7;
+  r.bsum = reinterpret_cast<double*>(w);
+  r.bw = r.bsum + nb;
+  return r;
+}
+
+__global__ void __launch_bounds__(AR_T) pop_stats_kernel(const float* __restrict__ logits, long long S, double theta,
+                                                         double* __restrict__ stats, int* __restrict__ resampled) {
+  __shared__ StatsLds L;
+  const long long p = blockIdx.x;
+  const int flag = logweight_stats_block(logits + p * S, S, theta, stats + 6 * p, L);
+  if (threadIdx.x == 0) resampled[p] = flag;
+}
+__global__ void __launch_bounds__(RS_T) pop_rs_max_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                          long long S, int nblk, long long P, char* ws, size_t stride) {
+  for (long long p = blockIdx.y; p < P; p += gridDim.y) {
+    if (gate[p]) rs_max_block(logits + p * S, S, rs_scratch(ws + p * stride, S, nblk).bmax);
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(RS_T) pop_rs_sum_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                          long long S, int nblk, long long P, char* ws, size_t stride,
+                                                          int phase) {
+  for (long long p = blockIdx.y; p < P; p += gridDim.y) {
+    if (gate[p]) {
+      const RsScratch w = rs_scratch(ws + p * stride, S, nblk);
+      rs_sum_block(logits + p * S, S, nblk, w.bmax, w.bsum, phase == 1 ? w.bw : w.bsum, phase);
+    }
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(RS_T) pop_rs_bins_kernel(const int* __restrict__ gate, const float* __restrict__ logits,
+                                                           long long S, int nblk, long long P, char* ws, size_t stride) {
+  for (long long p = blockIdx.y; p < P; p += gridDim.y) {
+    if (gate[p]) {
+      const RsScratch w = rs_scratch(ws + p * stride, S, nblk);
+      rs_bins_block(logits + p * S, S, nblk, w.bmax, w.bsum, w.bw, w.bins);
+    }
+    __syncthreads();
+  }
+}
+// pass E per population, as GLOBAL rows (p S + parent); the identity where the flag is clear.  logw_next (nullable): 0
+// where the population resampled, its log-weights where not.  This is the last pass, the bins were made from `logits` by
+// earlier launches and element k is copied only onto index k, so logw_next may be logits (no __restrict__ on either).
+__global__ void __launch_bounds__(256) pop_rs_search_kernel(const int* __restrict__ gate, const float* logits, long long S,
+                                                            int nblk, long long P, const double* __restrict__ u0, char* ws,
+                                                            size_t stride, long long* __restrict__ ids, float* logw_next) {
+  const float invS = (float)(1.0 / (double)S);
+  for (long long p = blockIdx.y; p < P; p += gridDim.y) {
+    const long long base = p * S;
+    const int flag = gate[p];
+    const float* bins = rs_scratch(ws + p * stride, S, nblk).bins;
+    const double u = u0[p];
+    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < S; k += (long long)gridDim.x * 256) {
+      ids[base + k] = base + (flag ? rs_search(bins, S, u, invS, k) : k);
+      if (logw_next) logw_next[base + k] = flag ? 0.0f : logits[base + k];
+    }
+  }
+}
+__global__ void __launch_bounds__(1024) pop_count_runs_kernel(const int* __restrict__ gate, const long long* __restrict__ ids,
+                                                              long long S, long long* __restrict__ n_unique) {
+  const long long p = blockIdx.x;
+  if (gate[p]) {
+    count_runs_block(ids + p * S, S, n_unique + p);  // a common offset does not change where the runs break
+  } else if (threadIdx.x == 0) {
+    n_unique[p] = S;
+  }
+}
+
 }  // namespace pita
 
 using namespace pita;
@@ -879,8 +969,8 @@ static inline long long rs_nblk(int64_t B) { return (B + RS_E - 1) / RS_E; }
 
 // workspace: float bins[B] | float bmax[nblk] | double bsum[nblk] | double bw[nblk]   (8-byte aligned sections)
 extern "C" size_t pita_resample_workspace_bytes(int64_t B) {
-  const size_t n = (size_t)(B > 0 ? B : 1), nb = (size_t)rs_nblk(B > 0 ? B : 1);
-  return ((n * 4 + 7) & ~(size_t)7) + ((nb * 4 + 7) & ~(size_t)7) + 2 * nb * 8;
+  const long long n = B > 0 ? B : 1;
+  return rs_scratch_bytes(n, rs_nblk(n));
 }
 
 extern "C" int pita_systematic_resample(const float* logits, int64_t B, double u0, int64_t* ids, void* workspace,
@@ -889,13 +979,9 @@ extern "C" int pita_systematic_resample(const float* logits, int64_t B, double u
   if (B == 0) return PITA_OK;
   PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_systematic_resample: workspace must be 8-byte aligned");
   const long long nb = rs_nblk(B);
-  char* w = static_cast<char*>(workspace);
-  float* bins = reinterpret_cast<float*>(w);
-  w += ((size_t)B * 4 + 7) & ~(size_t)7;
-  float* bmax = reinterpret_cast<float*>(w);
-  w += ((size_t)nb * 4 + 7) & ~(size_t)7;
-  double* bsum = reinterpret_cast<double*>(w);
-  double* bw = bsum + nb;
+  const RsScratch w = rs_scratch(workspace, B, nb);
+  float *bins = w.bins, *bmax = w.bmax;
+  double *bsum = w.bsum, *bw = w.bw;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(rs_max_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, logits, (long long)B, bmax);
   hipLaunchKernelGGL(rs_sum_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, logits, (long long)B, (int)nb, bmax, bsum, bsum, 0);
@@ -941,13 +1027,9 @@ extern "C" int pita_adaptive_resample(const float* logits, int64_t B, double u0,
     return PITA_OK;
   }
   const long long nb = rs_nblk(B);
-  char* w = static_cast<char*>(workspace);
-  float* bins = reinterpret_cast<float*>(w);
-  w += ((size_t)B * 4 + 7) & ~(size_t)7;
-  float* bmax = reinterpret_cast<float*>(w);
-  w += ((size_t)nb * 4 + 7) & ~(size_t)7;
-  double* bsum = reinterpret_cast<double*>(w);
-  double* bw = bsum + nb;
+  const RsScratch w = rs_scratch(workspace, B, nb);
+  float *bins = w.bins, *bmax = w.bmax;
+  double *bsum = w.bsum, *bw = w.bw;
   const int* gate = resampled;
   hipLaunchKernelGGL(logweight_stats_kernel, dim3(1), dim3(AR_T), 0, s, logits, (long long)B, theta, stats, resampled);
   hipLaunchKernelGGL(rs_max_gated_kernel, dim3((unsigned)nb), dim3(RS_T), 0, s, gate, logits, (long long)B, bmax);
@@ -985,6 +1067,42 @@ extern "C" int pita_population_resample(const float* logits, int64_t n_pop, int6
   hipLaunchKernelGGL(population_resample_kernel, dim3((unsigned)n_pop), dim3(AR_T),
                      ar_val_bytes(pop_size) + 2 * (size_t)pop_size, (hipStream_t)stream, logits, (int)pop_size, u0_dev, theta,
                      (long long*)ids, (long long*)n_unique, stats, resampled, logw_next);
+  PITA_LAUNCH_CHECK();
+  return PITA_OK;
+}
+
+// P copies of pita_systematic_resample's scratch, one per population (each a multiple of 8 bytes)
+extern "C" size_t pita_population_resample_blocks_workspace_bytes(int64_t n_pop, int64_t pop_size) {
+  return (size_t)(n_pop > 0 ? n_pop : 1) * pita_resample_workspace_bytes(pop_size);
+}
+
+extern "C" int pita_population_resample_blocks(const float* logits, int64_t n_pop, int64_t pop_size, const double* u0_dev,
+                                               double theta, int64_t* ids, int64_t* n_unique, double* stats, int* resampled,
+                                               float* logw_next, void* workspace, void* stream) {
+  PITA_REQUIRE(n_pop >= 1 && n_pop <= 0x7fffffffLL, "pita_population_resample_blocks: n_pop must be in [1, 2^31) (got %lld)",
+               (long long)n_pop);
+  PITA_REQUIRE(pop_size >= 1, "pita_population_resample_blocks: pop_size must be at least 1 (got %lld)",
+               (long long)pop_size);
+  PITA_REQUIRE(logits && u0_dev && ids && stats && resampled && workspace, "pita_population_resample_blocks: null argument");
+  PITA_REQUIRE(theta >= 0.0 && theta <= 1.0, "pita_population_resample_blocks: theta must be in [0, 1] (got %g)", theta);
+  PITA_REQUIRE(((uintptr_t)workspace & 7) == 0, "pita_population_resample_blocks: workspace must be 8-byte aligned");
+  const long long P = n_pop, S = pop_size, nb = rs_nblk(S), sb = (S + 255) / 256;
+  const size_t stride = pita_resample_workspace_bytes(S);
+  char* ws = static_cast<char*>(workspace);
+  const int* gate = resampled;
+  const unsigned gy = (unsigned)(P < 65535 ? P : 65535);
+  const dim3 pass((unsigned)nb, gy), search((unsigned)(sb < 8192 ? sb : 8192), gy);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pop_stats_kernel, dim3((unsigned)P), dim3(AR_T), 0, s, logits, S, theta, stats, resampled);
+  hipLaunchKernelGGL(pop_rs_max_kernel, pass, dim3(RS_T), 0, s, gate, logits, S, (int)nb, P, ws, stride);
+  hipLaunchKernelGGL(pop_rs_sum_kernel, pass, dim3(RS_T), 0, s, gate, logits, S, (int)nb, P, ws, stride, 0);
+  hipLaunchKernelGGL(pop_rs_sum_kernel, pass, dim3(RS_T), 0, s, gate, logits, S, (int)nb, P, ws, stride, 1);
+  hipLaunchKernelGGL(pop_rs_bins_kernel, pass, dim3(RS_T), 0, s, gate, logits, S, (int)nb, P, ws, stride);
+  hipLaunchKernelGGL(pop_rs_search_kernel, search, dim3(256), 0, s, gate, logits, S, (int)nb, P, u0_dev, ws, stride,
+                     (long long*)ids, logw_next);
+  if (n_unique)
+    hipLaunchKernelGGL(pop_count_runs_kernel, dim3((unsigned)P), dim3(1024), 0, s, gate, (const long long*)ids, S,
+                       (long long*)n_unique);
   PITA_LAUNCH_CHECK();
   return PITA_OK;
 }

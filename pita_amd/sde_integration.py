@@ -16,9 +16,10 @@ How the work is laid out on MI355X (differences from the reference are deliberat
     distinct parents it needs (_Comm.exchange_rows);
   * noise is Philox4x32-10 keyed by (seed, GLOBAL walker index, step): the result does not depend
     on the number of GPUs.  ``noise=`` injects recorded normals for parity tests.
-  * ``populations=P`` (an extension): the batch is P independent populations of at most 2 048 walkers, each resampled
-    on its own in one launch per event (pita_population_resample); events are rank-local, the log-weights and the event
-    log are gathered once after the loop.
+  * ``populations=P`` (an extension): the batch is P independent populations of any size, each resampled on its own --
+    in one launch per event up to 2 048 walkers (pita_population_resample), in a fixed number of launches beyond
+    (pita_population_resample_blocks); events are rank-local, the log-weights and the event log are gathered once after
+    the loop.
 ``sde_terms_all`` has N entries like the reference's (:150,:212).  By default each field is a ``TermStats`` (sum,
 sum of squares, count over the global batch, reduced on the device) that answers ``.mean()`` / ``.std()`` -- the only
 things the reference's callers ever ask of these tensors (energytemp_module.py:938-945,1132-1143);
@@ -42,7 +43,8 @@ from ._target import MalaPopulations
 from .data_utils import remove_mean
 from .metrics import logweight_stats
 from .sdes import SDETerms, TermStats, VEReverseSDE  # noqa: F401
-from .utils import MAX_POPULATION_SIZE, gather_rows, sample_cat_sys, sample_cat_sys_adaptive, sample_cat_sys_populations
+from .utils import (MAX_POPULATION_SIZE, gather_rows, sample_cat_sys, sample_cat_sys_adaptive,
+                    sample_cat_sys_population_blocks, sample_cat_sys_populations)
 
 
 def _scalar(v):
@@ -237,11 +239,12 @@ def _host_counts(counts):
     return counts
 
 
-def population_layout(Bg, world, populations, batch_size):
+def population_layout(Bg, world, populations, batch_size, max_size=MAX_POPULATION_SIZE):
     """``(S, populations per rank, clamp chunk)`` of a run of ``Bg`` walkers in ``populations`` independent populations
     over ``world`` ranks: S = Bg / populations walkers each, whole populations per rank, and the 0.9-quantile clamp of the
     debiased drift over chunks of ``min(batch_size or S, S)`` walkers, which must tile a population.  ValueError where
-    the walkers do not split evenly, a population exceeds what one block resamples (2 048), populations would straddle
+    the walkers do not split evenly, a population exceeds ``max_size`` (by default what one block resamples, 2 048; None:
+    no limit, the integrator's own call -- larger populations take the multi-block event), populations would straddle
     ranks or the clamp chunks would straddle populations."""
     Bg, world, P = int(Bg), int(world), int(populations)
     if P < 1:
@@ -249,8 +252,8 @@ def population_layout(Bg, world, populations, batch_size):
     if Bg < P or Bg % P != 0:
         raise ValueError(f"{Bg} walkers do not split into {P} populations of equal size")
     S = Bg // P
-    if S > MAX_POPULATION_SIZE:
-        raise ValueError(f"a population of {S} walkers exceeds the limit of {MAX_POPULATION_SIZE} (one block per population)")
+    if max_size is not None and S > max_size:
+        raise ValueError(f"a population of {S} walkers exceeds the limit of {max_size} (one block per population)")
     if P % world != 0:
         raise ValueError(f"{P} populations do not split over {world} ranks: populations never straddle ranks")
     chunk = S if not batch_size else min(int(batch_size), S)
@@ -365,13 +368,15 @@ class _GlobalEvents(_Events):
 class _PopulationEvents(_Events):
     """``populations=P``: the layout, this rank's columns of the run's uniforms [events, P] on the device (drawn or taken
     once, rank 0's on every rank) and the log, with one more row for ``resample_at_end``.  Every event is rank-local: one
-    pita_population_resample launch and the row gather; log-weights and log are gathered once, after the loop."""
+    pita_population_resample launch (S <= 2 048) or the fixed launches of pita_population_resample_blocks (larger S) and
+    the row gather; log-weights and log are gathered once, after the loop."""
 
     keep_order = True  # set-aside walkers return to their own rows: row r stays in population r // S
 
     def __init__(self, comm, Bg, P, batch_size, N, n_events, theta, resample_u, device, weighted):
         self.comm, self.P, self.N, self.theta = comm, P, N, theta
-        self.S, self.Pl, self.clamp_chunk = population_layout(Bg, comm.world, P, batch_size)
+        self.S, self.Pl, self.clamp_chunk = population_layout(Bg, comm.world, P, batch_size, max_size=None)
+        self.one_launch = self.S <= MAX_POPULATION_SIZE
         if resample_u is None:
             u = torch.rand((n_events, P), dtype=torch.float64)
         else:
@@ -398,7 +403,8 @@ class _PopulationEvents(_Events):
     def _launch(self, x, a, theta, row):
         u = self.u[self.next_event]
         self.next_event += 1
-        ids, _, _, _, a_next = sample_cat_sys_populations(a, self.Pl, theta, u, out=self.row(row))
+        resample = sample_cat_sys_populations if self.one_launch else sample_cat_sys_population_blocks
+        ids, _, _, _, a_next = resample(a, self.Pl, theta, u, out=self.row(row))
         return gather_rows(x, ids), a_next
 
     def event(self, x, a, step):
@@ -480,11 +486,11 @@ class WeightedSDEIntegrator:
         not have), and ``last_weight_stats`` holds the per-event diagnostics of the last run.
 
         ``populations``: None (one population: the whole batch, exactly the launches and bits of before) or P >= 1 -- the
-        batch is P independent populations of S = batch / P <= 2 048 walkers, rows [p S, (p + 1) S) being population p
+        batch is P independent populations of S = batch / P walkers (any S), rows [p S, (p + 1) S) being population p
         from the first to the last step and in everything returned.  Each population has its own ESS, decision, uniform,
         systematic resampling, distinct-parent count, quantile clamp and ``log_z``; every event is one launch
-        (``sample_cat_sys_populations``) plus the row gather on the rank's own walkers, with no collective, because
-        populations never straddle ranks.  ``resample_u`` is then [events, P] (event-major, ``resample_at_end`` last),
+        (``sample_cat_sys_populations``, S <= 2 048) or seven whatever P is (``sample_cat_sys_population_blocks``, larger
+        S) plus the row gather on the rank's own walkers, with no collective, because populations never straddle ranks.  ``resample_u`` is then [events, P] (event-major, ``resample_at_end`` last),
         ``last_weight_stats`` is filled whatever ``ess_threshold`` is, its per-event arrays are [N, P] and ``log_z`` is
         [P].  The one coupling between populations is the post-processing MALA chain of ``adaptive_mcmc=True``: its one
         step size adapts to the acceptance rate over the whole batch -- unless ``mcmc_per_population`` is set.

@@ -62,7 +62,8 @@ MAX_POPULATION_SIZE = 2048  # walkers one block of pita_population_resample hold
 
 def sample_cat_sys_populations(logits, n_pop, theta, u=None, out=None):
     """One resampling event for each of ``n_pop`` independent populations in ONE launch (pita_population_resample; an
-    extension).  ``logits`` [n_pop * S] holds the populations back to back, S <= 2 048; population p is decided and
+    extension).  ``logits`` [n_pop * S] holds the populations back to back, S <= 2 048 (a larger S is refused:
+    ``sample_cat_sys_population_blocks`` takes any); population p is decided and
     resampled exactly as ``sample_cat_sys_adaptive(S, logits[p * S:(p + 1) * S], theta, u[p])`` would, bit for bit and
     whatever ``n_pop`` and ``p`` are.  Returns ``(ids, resampled, stats, n_unique, logw_next)``, all device tensors and
     none of them read by the host here: ``ids`` int64 [n_pop * S] are GLOBAL rows (p * S + parent), so ``gather_rows``
@@ -72,6 +73,21 @@ def sample_cat_sys_populations(logits, n_pop, theta, u=None, out=None):
     ``u``: float64 [n_pop] uniforms in [0, 1), on the host or on the device (a device tensor is used as it is and not
     checked); None draws ``torch.rand(n_pop, dtype=float64)`` from torch's CPU generator.  ``out``: optional
     ``(resampled, stats, n_unique)`` to write into (rows of a caller's per-step buffers)."""
+    return _population_events("pita_population_resample", logits, n_pop, theta, u, out)
+
+
+def sample_cat_sys_population_blocks(logits, n_pop, theta, u=None, out=None):
+    """``sample_cat_sys_populations`` for populations of ANY size S (pita_population_resample_blocks; an extension): the
+    same arguments, the same return tuple and the same contract -- population p is decided and resampled exactly as
+    ``sample_cat_sys_adaptive(S, logits[p * S:(p + 1) * S], theta, u[p])`` would, bit for bit and whatever ``n_pop`` and
+    ``p`` are.  Always the multi-block route: at most seven launches per call whatever ``n_pop`` is (one statistics block
+    per population, the five passes of ``sample_cat_sys`` over a (block, population) grid, the run count), so for
+    S <= 2 048 it returns what the one launch of ``sample_cat_sys_populations`` returns, in more launches."""
+    return _population_events("pita_population_resample_blocks", logits, n_pop, theta, u, out)
+
+
+def _population_events(entry, logits, n_pop, theta, u, out):
+    """The host side the two population entry points share: ``entry`` and ``entry``_workspace_bytes of the library."""
     logits = _lib.dev_tensor(logits, "logits").reshape(-1)
     n_pop = int(n_pop)
     if n_pop < 1 or logits.shape[0] % n_pop != 0:
@@ -96,11 +112,10 @@ def sample_cat_sys_populations(logits, n_pop, theta, u=None, out=None):
                torch.empty(n_pop, device=dev, dtype=torch.int64))
     resampled, stats, n_unique = out
     L = _lib.lib()
-    ws = _workspace(L.pita_population_resample_workspace_bytes(n_pop, S), dev)
-    _lib.check(L.pita_population_resample(logits.data_ptr(), n_pop, S, u.data_ptr(), float(theta), ids.data_ptr(),
-                                          n_unique.data_ptr(), stats.data_ptr(), resampled.data_ptr(),
-                                          logw_next.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),
-               "pita_population_resample")
+    ws = _workspace(getattr(L, entry + "_workspace_bytes")(n_pop, S), dev)
+    _lib.check(getattr(L, entry)(logits.data_ptr(), n_pop, S, u.data_ptr(), float(theta), ids.data_ptr(),
+                                 n_unique.data_ptr(), stats.data_ptr(), resampled.data_ptr(), logw_next.data_ptr(),
+                                 ws.data_ptr(), _lib.stream_ptr(dev)), entry)
     return ids, resampled, stats, n_unique, logw_next
 
 
