@@ -871,6 +871,53 @@ int pita_dihedral_histogram2d(const float* x, const float* logw /*nullable*/, in
                               int nbins_b, unsigned long long* wsum, unsigned long long* counts, double* info,
                               void* stream);
 
+/* ---------------------------------------------------------------- weighted per-population mix-RBF Gram sums (MMD)
+ * The sample-space member of the family above.  The reference's mmd.py (mix_rbf_mmd2, called with the bandwidths 0.01,
+ * 0.1, 1, 10, 100) was never restated in oracle/: THIS definition is the specification -- unpinned by construction, like
+ * DW4 and the POT W2.  Mix-RBF kernel k(x, y) = sum_s exp(-gamma_s |x - y|^2), gamma_s = 1 / (2 sigma_s^2).
+ *
+ * a: device float [n_pop * pop_size, dim], population p in rows [p * pop_size, (p + 1) * pop_size) (the integrator's
+ * layout), relative row weights w_i from logw_a.  b: device float [n_b, dim], ONE set shared by every population, row
+ * weights v_j from logw_b.  logw_*: device float, nullable = unit weights.  The call writes
+ *  sums   double [n_pop, n_gamma]  S[p, s] = sum_i sum_j w_i v_j exp(-gamma_s |a_i - b_j|^2), i over population p
+ *  info_a double [n_pop, 5]        {m_p, sum w, sum w^2, n_bad, n_neg_inf}
+ *  info_b double [5]               the same for b (nullable: not wanted)
+ * With b == NULL (self mode) population p is summed against itself, every ordered pair and the diagonal included; then
+ * logw_b must be NULL and n_b 0, and info_b is ignored.  1 <= dim <= 768 (the force field's 256 atoms x 3), 1 <= n_gamma
+ * <= 16, every gamma finite and >= 0; gammas is a HOST array, read in the call, and travels as kernel arguments.  All
+ * argument checks run before any device call (PITA_EINVAL); sizes whose block or element counts overflow are
+ * PITA_EUNSUPPORTED.  workspace: 8-byte aligned device scratch of at least pita_rbf_gram_workspace_bytes(n_pop, pop_size,
+ * n_b) bytes (n_b = 0: self mode; 0 is returned for sizes the call refuses).  Outputs are overwritten.
+ *
+ * Weights, the family's convention: m_p = max over the finite log-weights of the population (0 when there is none), w =
+ * exp((double)logw - m_p) rounded to fp32 ONCE; a row whose logw is NaN or +inf, or which holds a coordinate that is
+ * not finite (as pita_weighted_moments does for values), is left out and counted in n_bad; a row with logw = -inf among
+ * the others has weight 0 and is counted in n_neg_inf.  A weights pass writes the fp32 row weights (0 for a row left
+ * out) to the workspace; sum w and sum w^2 are sums of those fp32 weights, in double, in pita_weighted_moments' fixed
+ * order.  A row of weight 0 contributes exactly 0 by SELECTION: its squared distance is replaced by 0 before the
+ * exponential, so that NaN coordinates never meet a product.
+ *
+ * Pair arithmetic, fp32, vector pipe, no contraction beyond the fmaf named here: d_k = a_k - b_k first, then s =
+ * fmaf(d_k, d_k, s) over k in index order from s = 0; s = min(s, FLT_MAX) (finite rows whose distance overflows: gamma =
+ * 0 still gives 1, every other gamma 0); e = exp2(c_s * s) by the hardware's exp2 (about 1 ulp), c_s = (float)(-gamma_s *
+ * log2 e) computed in double on the host; term = (w_i * v_j) * e.  Two bit-identical rows therefore give s = 0 and e = 1
+ * EXACTLY for every gamma -- the reason the distance does not go through |a|^2 + |b|^2 - 2 a.b or the matrix pipe: after
+ * a resampling event many walkers are copies, and the rounding noise of the expanded form would be multiplied by gamma
+ * (5 000 at sigma = 0.01).  fp32 accumulation is confined to the 16 terms a thread holds of one 64 x 64 tile pair (its 4
+ * x 4 sub-tile, a-row outer, b-row inner); everything above is double.
+ *
+ * Reduction: no floating-point atomics.  A block takes one (population, a-tile of 64 rows) and every nbg-th b-tile,
+ * nbg a function of (pop_size, n_b) alone; threads add their tiles in double, xor-shuffle wave reduction, the four
+ * wave partials in index order, one partial per block; a second kernel adds a population's partials in a fixed order.
+ * Self mode visits only the tile pairs jb >= ia and counts an off-diagonal tile twice (a multiplication by 2 in double).
+ * The bits of population p are the same from run to run and depend neither on n_pop nor on p (a call on its slice alone
+ * gives the same bits); they DO depend on the order of the rows, as pita_weighted_moments' do. */
+size_t pita_rbf_gram_workspace_bytes(int64_t n_pop, int64_t pop_size, int64_t n_b);
+int pita_rbf_gram_sums(const float* a, const float* logw_a /*nullable*/, int64_t n_pop, int64_t pop_size,
+                       const float* b /*nullable = self mode*/, const float* logw_b /*nullable*/, int64_t n_b, int dim,
+                       const double* gammas /*HOST, n_gamma entries*/, int n_gamma, double* sums, double* info_a,
+                       double* info_b /*nullable*/, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

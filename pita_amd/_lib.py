@@ -188,6 +188,9 @@ _PROTOS = {
     "pita_dihedral_angles": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "pita_dihedral_histogram2d": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_int,
                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pita_rbf_gram_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "pita_rbf_gram_sums": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                   POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

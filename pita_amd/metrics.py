@@ -462,3 +462,101 @@ def ramachandran_histogram(samples: torch.Tensor, pair_quads, bins: int = 64, lo
                                                     shape[2], tb.data_ptr(), shape[3], raw.data_ptr(), counts.data_ptr(),
                                                     info.data_ptr(), _lib.stream_ptr(x.device)), "pita_dihedral_histogram2d")
     return DihedralHistogram(raw, counts, info, ea, eb)
+
+
+MMD_SIGMAS = (0.01, 0.1, 1.0, 10.0, 100.0)  # the bandwidths the reference passes to its mix_rbf_mmd2
+
+
+def _rbf_gram(a, lw_a, P, S, b, lw_b, gammas):
+    """One pita_rbf_gram_sums call: (sums [P, n] , info_a [P, 5], info_b [5] or None) as float64 numpy arrays."""
+    import ctypes
+
+    from . import _lib
+
+    n, M = len(gammas), 0 if b is None else b.shape[0]
+    L = _lib.lib()
+    nbytes = L.pita_rbf_gram_workspace_bytes(P, S, M)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(P * n + 5 * P + 5, dtype=torch.float64, device=a.device)
+    sums, info_a, info_b = out[:P * n], out[P * n:P * n + 5 * P], out[P * n + 5 * P:]
+    g = (ctypes.c_double * n)(*gammas)
+    _lib.check(L.pita_rbf_gram_sums(a.data_ptr(), _lib.ptr(lw_a), P, S, _lib.ptr(b), _lib.ptr(lw_b), M, a.shape[1], g, n,
+                                    sums.data_ptr(), info_a.data_ptr(), 0 if b is None else info_b.data_ptr(), ws.data_ptr(),
+                                    _lib.stream_ptr(a.device)), "pita_rbf_gram_sums")
+    h = out.cpu().numpy()
+    return h[:P * n].reshape(P, n).copy(), h[P * n:P * n + 5 * P].reshape(P, 5).copy(), None if b is None else h[-5:].copy()
+
+
+def rbf_mmd2(samples: torch.Tensor, test_set: torch.Tensor, sigma_list=MMD_SIGMAS, logweights: torch.Tensor = None,
+             populations: int = 1, test_logweights: torch.Tensor = None, biased: bool = True, test_self=None):
+    """Squared mix-RBF MMD between every population of ``samples`` [B, D] and ``test_set`` [M, D], importance-weighted,
+    on the device (pita_rbf_gram_sums: fused fp32 pair kernel with the difference first, double above it; the pair
+    matrix is never written).  The reference's mmd.py is not restated in oracle/: the definition in include/pita_hip.h
+    is the specification.  k(x, y) = sum_s exp(-|x - y|^2 / (2 sigma_s^2)); rows of population p carry the relative
+    weights w of ``logweights`` (None = unit), test rows v of ``test_logweights``.  With S_xx, S_xy, S_yy the weighted
+    Gram sums per bandwidth (diagonal included), W = sum w, W2 = sum w^2 and V, V2 likewise:
+      biased (the reference's default):  k_xx = S_xx / W^2,  k_yy = S_yy / V^2,  k_xy = S_xy / (W V);
+      unbiased:  k_xx = (S_xx - W2) / (W^2 - W2), k_yy likewise (NaN where the denominator is not positive), k_xy as above;
+      mmd2[p] = sum_s (k_xx + k_yy - 2 k_xy), neither clamped nor rooted.
+    The caller chooses the features (GMM coordinates, peptide coordinates, anything [., D], D <= 768).  Three device
+    calls: self on the samples, cross, self on the test set; the last is skipped when ``test_self`` -- the entry of that
+    name of an earlier result against the same test set, weights and bandwidths -- is passed back in.
+    Returns a dict of float64 numpy arrays: ``mmd2`` [P], ``mmd2_per_sigma``, ``k_xx``, ``k_xy`` [P, n_sigma], ``k_yy``
+    [n_sigma], ``sum_w``, ``sum_w2``, ``n_bad``, ``n_neg_inf``, ``log_scale`` [P], and ``test_self`` = {"sums" [n_sigma],
+    "info" [5] = {m, V, V2, n_bad, n_neg_inf}, "gammas" [n_sigma], "rows"}.  A population with sum w = 0 gives NaN."""
+    import numpy as np
+    from . import _lib
+
+    sig = np.asarray(list(sigma_list), dtype=np.float64).reshape(-1)
+    if sig.size < 1 or sig.size > 16 or not (np.isfinite(sig).all() and (sig > 0).all()):
+        raise ValueError(f"sigma_list: expected 1 to 16 finite positive bandwidths, got {sigma_list}")
+    gammas = 1.0 / (2.0 * sig * sig)
+    if not np.isfinite(gammas).all():
+        raise ValueError(f"sigma_list: 1 / (2 sigma^2) overflows for {sigma_list}")
+    if samples.dim() != 2 or test_set.dim() != 2 or samples.shape[1] != test_set.shape[1] or not 1 <= samples.shape[1] <= 768:
+        raise ValueError(f"samples [B, D] and test_set [M, D] with 1 <= D <= 768 expected, got {tuple(samples.shape)} and "
+                         f"{tuple(test_set.shape)}")
+    if samples.device != test_set.device:
+        raise ValueError(f"samples are on {samples.device}, test_set on {test_set.device}")
+    P, S, _ = _population_args(samples.shape[0], None, populations, None)
+    M = test_set.shape[0]
+    if M < 1:
+        raise ValueError("test_set is empty")
+    for name, t, rows in (("logweights", logweights, samples.shape[0]), ("test_logweights", test_logweights, M)):
+        if t is not None and (t.numel() != rows or t.device != samples.device):
+            raise ValueError(f"{name}: expected {rows} entries on {samples.device}, got {t.numel()} on {t.device}")
+    if test_self is not None:
+        ok = isinstance(test_self, dict) and {"sums", "info", "gammas", "rows"} <= set(test_self)
+        if not (ok and np.array_equal(np.asarray(test_self["gammas"], np.float64), gammas) and int(test_self["rows"]) == M
+                and np.shape(test_self["sums"]) == (sig.size,) and np.shape(test_self["info"]) == (5,)):
+            raise ValueError("test_self: not the entry of an rbf_mmd2 result with this test set size and these bandwidths")
+    x = _lib.dev_tensor(samples, "samples")
+    y = _lib.dev_tensor(test_set, "test_set")
+    _, _, lw = _population_args(x.shape[0], logweights, populations, x.device)
+    _, _, lv = _population_args(M, test_logweights, 1, x.device)
+    g = [float(v) for v in gammas]
+    s_xx, info_x, _ = _rbf_gram(x, lw, P, S, None, None, g)
+    s_xy, _, info_y = _rbf_gram(x, lw, P, S, y, lv, g)
+    if test_self is None:
+        s_yy, _, _ = _rbf_gram(y, lv, 1, M, None, None, g)
+        test_self = {"sums": s_yy[0], "info": info_y, "gammas": gammas.copy(), "rows": M}
+    s_yy, info_y = np.asarray(test_self["sums"], np.float64), np.asarray(test_self["info"], np.float64)
+    W, W2, V, V2 = info_x[:, 1:2], info_x[:, 2:3], info_y[1], info_y[2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if biased:
+            k_xx = np.where(W > 0, s_xx / (W * W), np.nan)
+            k_yy = s_yy / (V * V) if V > 0 else np.full_like(s_yy, np.nan)
+        else:
+            dx, dy = W * W - W2, V * V - V2
+            k_xx = np.where(dx > 0, (s_xx - W2) / dx, np.nan)
+            k_yy = (s_yy - V2) / dy if dy > 0 else np.full_like(s_yy, np.nan)
+        k_xy = np.where(W * V > 0, s_xy / (W * V), np.nan)
+    per = k_xx + k_yy[None, :] - 2.0 * k_xy
+    return {"mmd2": per.sum(1), "mmd2_per_sigma": per, "k_xx": k_xx, "k_xy": k_xy, "k_yy": k_yy, "sum_w": info_x[:, 1].copy(),
+            "sum_w2": info_x[:, 2].copy(), "n_bad": info_x[:, 3].copy(), "n_neg_inf": info_x[:, 4].copy(),
+            "log_scale": info_x[:, 0].copy(), "test_self": test_self}
+
+
+def mix_rbf_mmd2(X: torch.Tensor, Y: torch.Tensor, sigma_list=MMD_SIGMAS, biased: bool = True) -> float:
+    """The reference's signature: one unweighted sample set against another, ``rbf_mmd2(...)["mmd2"][0]``."""
+    return float(rbf_mmd2(X, Y, sigma_list, biased=biased)["mmd2"][0])
