@@ -503,14 +503,22 @@ int pita_egnn_div_work(const pita_egnn_t* net, double* mfma16_per_walker, double
  * logp_target NULL = no pinning.  All arrays are device pointers: x, D_E, jtx_E, D_S, drift_X [B,D]; the rest [B].
  * dot_parts ([B, 2] from pita_egnn_vjp, nullable): when given, E = be [|x|^2/(2(1+h)) - s1/h] and
  * dE/dh = be [-|x|^2/(2(1+h)^2) + s1/h^2 - s2/h] with (s1, s2) = dot_parts[b] -- the same quantities in the
- * reference's own well-conditioned form; NULL keeps the forms through <D_E, x> and dot_h. */
+ * reference's own well-conditioned form; NULL keeps the forms through <D_E, x> and dot_h.
+ * The clamp of U0 is torch.clamp's: +-inf become -+1e3, and a NaN logp_target stays NaN -- that walker's Ut, dUt_dt and
+ * drift_A are NaN (its drift_X, divergence_score and cross_term do not read logp_target), no other walker is touched.
+ * B = 0 returns PITA_OK without a launch; B < 0, D < 1, a null required pointer with B > 0 and non-zero pin weights
+ * without logp_target are PITA_EINVAL. */
 int pita_fk_assemble(const float* x, const float* h, const float* g2, const float* dhdt, const float* D_E,
                      const float* jtx_E, const float* dot_h, const float* dot_parts /*nullable*/, const float* D_S,
                      const float* trace_S, float gamma, float dgamma, const float* beta_e /*nullable*/, const float* beta_s /*nullable*/, float pin_w,
                      float pin_dw, const float* logp_target /*nullable*/, float* drift_X, float* drift_A, float* div_bt,
                      float* cross, float* dUdt, float* Ut, int64_t B, int D, void* stream);
 /* K11: in place a[c] = min(a[c], quantile_q(a over its chunk)), chunks of `chunk` consecutive walkers, linear
- * interpolation like torch.quantile (sdes.py:230; sde_integration.py:179). */
+ * interpolation like torch.quantile (sdes.py:230; sde_integration.py:179).
+ * NaN entries -- a departure from torch, which turns the whole chunk into NaN: a NaN keeps its place and its value; in
+ * the order statistics it sorts above +inf (by its bit pattern: a NaN with the sign bit set sorts below -inf); the other
+ * entries are clamped by the quantile of those keys; a chunk whose quantile itself comes out NaN is left unchanged
+ * (fminf returns the entry). */
 int pita_quantile_clamp(float* a, int64_t B, int64_t chunk, float q, void* stream);
 
 /* ---------------------------------------------------------------- fused sampler (K5+K7+K8)

@@ -229,8 +229,17 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t walker, i
   // Box-Muller on the transcendental unit: v_log_f32 is log2, v_sin/v_cos take revolutions (no range reduction
   // needed for u in (0,1)); absolute error of a normal ~1e-6, far below the sampler's fp32 noise floor
   const float kM2Ln2 = -1.38629436111989062f;  // -2 ln 2
-  float r0 = __builtin_amdgcn_sqrtf(kM2Ln2 * __builtin_amdgcn_logf(u0));
-  float r1 = __builtin_amdgcn_sqrtf(kM2Ln2 * __builtin_amdgcn_logf(u2));
+  float q0 = kM2Ln2 * __builtin_amdgcn_logf(u0), q1 = kM2Ln2 * __builtin_amdgcn_logf(u2);  // -2 ln u
+  // The float32 sum (c >> 8) + 0.5f drops the half-ulp offset for words k >= 2^23 (ties to even): u is a multiple of 2^-24
+  // there (1.0 for the last word).  That only matters where 1 - u is a few 2^-24 -- at 2^24 - k = 3 it made r 11 % short,
+  // a normal 4.5e-5 off the documented sqrt(-2 ln((k + 0.5) / 2^24)) -- so the last 64 words take -2 ln(1 - e) = 2 e + e^2
+  // (+ 2 e^3 / 3 < 1e-16) from e = 1 - u = (2^24 - k - 0.5) / 2^24, which float32 holds exactly.  Every other draw keeps
+  // its bits; just above the cut the rounding of u costs a normal at most 1.1e-5.
+  const uint32_t t0 = 16777216u - (c[0] >> 8), t1 = 16777216u - (c[2] >> 8);
+  const float e0 = ((float)t0 - 0.5f) * s, e1 = ((float)t1 - 0.5f) * s;
+  q0 = t0 <= 64u ? e0 * (2.0f + e0) : q0;
+  q1 = t1 <= 64u ? e1 * (2.0f + e1) : q1;
+  float r0 = __builtin_amdgcn_sqrtf(q0), r1 = __builtin_amdgcn_sqrtf(q1);
   float s0 = __builtin_amdgcn_sinf(u1), c0 = __builtin_amdgcn_cosf(u1);
   float s1 = __builtin_amdgcn_sinf(u3), c1 = __builtin_amdgcn_cosf(u3);
   z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;

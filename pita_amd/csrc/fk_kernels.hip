@@ -79,7 +79,10 @@ __global__ void __launch_bounds__(256) fk_assemble_kernel(FkParams p) {
       }
       float Ut = Et, dUdt = dEdt;
       if (p.logp_target) {
-        const float U0 = fminf(fmaxf(-p.logp_target[b], -1e3f), 1e3f);
+        // torch.clamp keeps a NaN (energy_net.py:44); fmaxf / fminf return their OTHER operand for one, which made a NaN
+        // target log-density U0 = -1000 and the walker's Ut, dUt_dt and drift_A finite
+        const float nlp = -p.logp_target[b];
+        const float U0 = (nlp != nlp) ? nlp : fminf(fmaxf(nlp, -1e3f), 1e3f);
         Ut = p.pin_w * U0 + (1.0f - p.pin_w) * Et;
         dUdt = p.pin_dw * (U0 - Et) + (1.0f - p.pin_w) * dEdt;
       }
@@ -205,7 +208,11 @@ __global__ void __launch_bounds__(QT) quantile_clamp_kernel(float* __restrict__ 
   }
   const float diff = vhi - vlo;
   const float quant = (w < 0.5f) ? fmaf(w, diff, vlo) : vhi - diff * (1.0f - w);  // at::lerp
-  for (long long i = threadIdx.x; i < n; i += QT) ac[i] = fminf(ac[i], quant);
+  // a NaN entry keeps its value (fminf alone would hand it the quantile); a NaN quantile leaves the chunk as it is
+  for (long long i = threadIdx.x; i < n; i += QT) {
+    const float v = ac[i];
+    ac[i] = (v != v) ? v : fminf(v, quant);
+  }
 }
 
 }  // namespace pita

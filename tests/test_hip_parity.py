@@ -1174,20 +1174,7 @@ def test_philox_normals(pa):
     assert abs(torch.corrcoef(v[:, :4].T)[0, 1].item()) < 1e-2
 
 
-def _philox_normals_host(seed, walkers, step, particles):
-    """Philox4x32-10 + Box-Muller as documented in include/pita_hip.h, in numpy (uint64 / float64)."""
-    M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-    w, pt = np.meshgrid(np.asarray(walkers, dtype=np.uint64), np.asarray(particles, dtype=np.uint64), indexing="ij")
-    mask = np.uint64(0xFFFFFFFF)
-    c = [w & mask, w >> np.uint64(32), np.full_like(w, step & 0xFFFFFFFF), pt ^ np.uint64(((step >> 32) << 20) & 0xFFFFFFFF)]
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = np.uint64(M0) * c[0], np.uint64(M1) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
-        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    u = [((ci >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 for ci in c]
-    r0, r1 = np.sqrt(-2 * np.log(u[0])), np.sqrt(-2 * np.log(u[2]))
-    return np.stack([r0 * np.cos(2 * np.pi * u[1]), r0 * np.sin(2 * np.pi * u[1]), r1 * np.cos(2 * np.pi * u[3])], -1)
+from tests._step_shapes import _philox_normals_host  # noqa: E402  (shared with tests/test_step_shapes_gpu.py)
 
 
 def test_philox_matches_host_restatement(pa):
